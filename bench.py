@@ -2,6 +2,8 @@
 """Headline benchmark: SANA-1.6B 1024 px bf16 training step, images/sec (whole job), on N MI355X.
 
     python bench.py --gpus 1 --steps 30 --warmup 5
+    python bench.py --gpus 1 --steps 30 --warmup 5 --full   (+ the side measurements below marked [--full])
+    python bench.py --gpus 1 --steps 30 --warmup 5 --dump-outputs DIR   (+ the last timed step's outputs as .npy: dump_outputs)
     python bench.py --gpus N --steps K --warmup W          (no launcher around it: starts its own ranks, see self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -13,18 +15,21 @@ N > 1), global-norm clip and AdamW.  B = 8 images per GPU (BASELINE config 2), w
 the concatenated text embeddings) are resident in HBM before the timed region; weights are random-init of the
 1.6 B architecture (no checkpoints offline).
 
-The JSON line carries, besides the driver's contract:
-  roofline      dominant kernel = the MFMA GEMM family.  achieved = algorithmic FLOPs of every GEMM launch in the
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the JSON line; everything measured
+after the timed region besides that runs only with --full.  The JSON line carries, besides the driver's contract (metric,
+value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step):
+  roofline      [--full] dominant kernel = the MFMA GEMM family.  achieved = algorithmic FLOPs of every GEMM launch in the
                 timed region (2*M*N*K each) / the summed HIP-event durations of those launches, recorded live on the
                 launch stream; peak = 2500 TFLOP/s dense bf16 (MI355X_MICROARCH.md).
   mfma_util_step  whole-step figure: algorithmic training FLOPs (6 x MAC, SURVEY.md 8d: 9.285 TFLOP/image at
                 N=1024,T=512) x img/s/GPU / 2.5e15.
-  comm          (N > 1, or YAT_DDP_FORCE=1 on one GPU) the data-parallel exchange: transport, buckets and bytes reduced per
-                step, per-bucket collective time from HIP events on the communication stream, the step with the collective
+  comm          [--full] (N > 1, or YAT_DDP_FORCE=1 on one GPU) the data-parallel exchange: transport, buckets and bytes
+                reduced per step, per-bucket collective time from HIP events on the communication stream, the step with the collective
                 switched off on the same inputs (exposed time = the difference), how long the optimizer waited, overlap
                 fraction, the RCCL channel cap in force (--rccl-channels N sets NCCL_MAX_NCHANNELS); with --lokr / --lora the
                 latency of the adapter set's single small all-reduce.
-  cpu_baseline  the CPU oracle (torch restatement of the reference path; diffusers is absent offline) timed on this
+  host_enqueue_ms_per_step  [--full] host time to enqueue one step onto an idle GPU (one extra step per bucket).
+  cpu_baseline  [--full] the CPU oracle (torch restatement of the reference path; diffusers is absent offline) timed on this
                 box's host cores on a bounded sample (rank 0, N=1 only).
 """
 from __future__ import annotations
@@ -118,6 +123,42 @@ def cpu_baseline(state_dict, cfg_layers=20):
                        f"T=512, fwd+bwd+clip+AdamW, 1 warm-up ({times[0]:.2f}s) + {len(timed)} timed steps "
                        f"({', '.join(f'{t:.2f}s' for t in timed)}), measured not extrapolated"),
             "cpu_model": cpu}
+
+
+DUMP_SAMPLE = 1 << 22          # positions of each flat buffer that --dump-outputs writes (16 MB each in float32)
+
+
+def dump_positions(n):
+    """The positions of a flat buffer of ``n`` elements that --dump-outputs writes: DUMP_SAMPLE of them drawn with seed 0 and
+    sorted (int64 CPU tensor), or None for the whole buffer when it is no longer than that."""
+    if n <= DUMP_SAMPLE:
+        return None
+    return torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+
+
+def dump_outputs(out_dir, trained, opt, loss):
+    """``--dump-outputs DIR``: what the timed path hands its caller after its last step, as float32 ``DIR/<name>.npy``, so
+    that two builds run with the same arguments (same seeded inputs) can be compared output for output:
+      loss           the last step's loss
+      grad_norm      the global gradient norm the clip computed in that step
+      params_sample  the trained flat parameters after its AdamW update, at DUMP_SAMPLE fixed positions
+      grads_sample   the flat gradients of its backward, at the same positions
+    The positions are those of ``dump_positions`` (the whole buffer when it is no longer than DUMP_SAMPLE): 32 MB in all."""
+    import numpy as np
+    torch.cuda.synchronize()
+    n = trained.numel_flat
+    idx = dump_positions(n)
+    if idx is not None:
+        idx = idx.to(trained.flat_param.device)
+
+    def take(buf):
+        return (buf[:n] if idx is None else buf[idx]).float().cpu().numpy()
+    arrays = {"loss": np.asarray([float(loss)], dtype=np.float32), "grad_norm": opt.grad_norm.float().cpu().numpy(),
+              "params_sample": take(trained.flat_param), "grads_sample": take(trained.flat_grad)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log(f"outputs of the last timed step written to {out_dir}: " + ", ".join(f"{k} {v.shape}" for k, v in arrays.items()))
 
 
 def run_from_shards(args, rank, world, local_rank):
@@ -231,6 +272,9 @@ def run_from_shards(args, rank, world, local_rank):
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = te.item()
     loss_val = float(trainer.loss_history[-1])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, trainer.adapters if trainer.adapters is not None else trainer.model, trainer.optimizer,
+                     loss_val)
     if rank == 0:
         cfg = trainer.model.cfg
         # text rows computed per image: the prompts' own lengths (uniform 20..300 in the synthetic shards, mean 160) when
@@ -328,7 +372,16 @@ def main():
     ap.add_argument("--coalesce", type=int, default=1, help="consecutive gradient buckets per collective (1 = one per block)")
     ap.add_argument("--phases", default=None, metavar="FILE",
                     help="after the timed region, time the phases of 6 steps with HIP events and write them to FILE")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the side measurements: host enqueue of one step onto an idle GPU, "
+                         "the data-parallel diagnostics (`comm`), the serialized GEMM / optimizer roofline pass (--gemm-detail "
+                         "needs it) and the CPU-oracle baseline.  Without it a run sets up, warms up, times --steps steps, "
+                         "writes --dump-outputs and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32; see dump_outputs)")
     args = ap.parse_args()
+    if args.gemm_detail and not args.full:
+        ap.error("--gemm-detail is written by the roofline pass, which runs with --full only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))      # (before anything touches the GPU or rewires stdout)
     # stdout carries exactly one JSON line.  Libraries do not know that: RCCL prints its version block on stdout when the
@@ -524,16 +577,19 @@ def main():
         elapsed = te.item()
     loss_val = loss_dev.item()
     log(f"timed region: {elapsed:.3f}s for {args.steps} steps, loss={loss_val:.4f}")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, trained, opt, loss_val)
     # host cost of one step: enqueue onto an idle GPU (nothing pushes back), every bucket's launch plan already recorded
     host_ms = []
-    for i in range(len(BUCKETS)):
+    if args.full:
+        for i in range(len(BUCKETS)):
+            barrier()
+            th = time.perf_counter()
+            step(args.warmup + args.steps + i)
+            host_ms.append(1e3 * (time.perf_counter() - th))
         barrier()
-        th = time.perf_counter()
-        step(args.warmup + args.steps + i)
-        host_ms.append(1e3 * (time.perf_counter() - th))
-    barrier()
-    log(f"host enqueue of one step onto an idle GPU: {min(host_ms):.1f} ms (per bucket: {', '.join(f'{v:.1f}' for v in host_ms)}; "
-        f"launch plans {'on' if model.use_plans else 'off'})")
+        log(f"host enqueue of one step onto an idle GPU: {min(host_ms):.1f} ms (per bucket: "
+            f"{', '.join(f'{v:.1f}' for v in host_ms)}; launch plans {'on' if model.use_plans else 'off'})")
 
     # ---- data-parallel diagnostics (after the timed region; SURVEY 8(d) C4 / C5: "report overlap fraction", "report all-reduce
     # latency for the ~MB-scale gradient set"; replaces what Accelerate's DDP hides behind common/trainer.py:253,344).  Three
@@ -542,7 +598,7 @@ def main():
     # overlap and CU interference included; and a pass with HIP events around every bucket's collective on the communication
     # stream and around the compute stream's wait for it.  Every rank runs them (collectives), rank 0 reports.
     comm = None
-    if ddp is not None:
+    if ddp is not None and args.full:
         # A failure on ONE rank must not leave the others inside a collective: every pass ends with an agreement (all-reduce MAX
         # of a local error flag) and all ranks abandon the diagnostics together; the arithmetic on the harvested events is
         # local and has its own guard.  (A rank that dies INSIDE a pass still strands its peers until the process-group
@@ -699,7 +755,7 @@ def main():
     # their individual durations overlap; the per-kernel figure is therefore taken with the streams serialized
     # (YAT_SERIAL=1 behaviour), same kernels, same shapes, same inputs.
     timer = None
-    if not args.no_gemm_timer:          # every rank runs it (the DDP collectives need all of them); rank 0 reports
+    if args.full and not args.no_gemm_timer:     # every rank runs it (the DDP collectives need all of them); rank 0 reports
         saved = (model.side_wgrad, opt.overlap_update, model.fwd_chains)
         model.side_wgrad, opt.overlap_update, model.fwd_chains = False, False, 1
         step(0)
@@ -734,10 +790,11 @@ def main():
                        "num_layers": cfg.num_layers, "params": model.numel_flat},
             "loss": loss_val,
             "hbm_peak_gb": torch.cuda.max_memory_allocated(dev) / 2 ** 30,
-            "host_enqueue_ms_per_step": min(host_ms),
             "mfma_util_step": (flops / args.steps / (elapsed / args.steps)) / (PEAK_BF16_TFLOPS * 1e12),
             "algorithmic_tflop_per_step": flops / args.steps / 1e12,
         }
+        if host_ms:
+            res["host_enqueue_ms_per_step"] = min(host_ms)
         if comm is not None:
             res["comm"] = comm
         if getattr(ops, "DIAGNOSTIC_INVALID", None):   # set only by scripts/step_ablation.py (kernel families skipped): NOT a
@@ -793,7 +850,7 @@ def main():
                     f.write(f"{lay:4s} {M_:7d} {N_:6d} {K_:6d} {act:>5s} {int(gt):3d} {int(rs):3d} {int(ax):3d} "
                             f"{n / args.roofline_steps:9.1f} {1e3 * ms / n:9.1f} {fl * n / (ms * 1e-3) / 1e12:9.1f} "
                             f"{ms / args.roofline_steps:9.3f}\n")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 model.join_pending_update()
                 sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}

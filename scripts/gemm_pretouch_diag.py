@@ -6,7 +6,7 @@ read pass over the operands named in PRETOUCH:  a | b | ab | none | dup (the lau
 launches of the real step in their real order, the in-step time with operand A / B / both brought back into the 256 MB
 Infinity Cache right before the launch -- the prize a deeper DMA lookahead or an operand warmer can win at most.
 
-    PRETOUCH=ab python scripts/gemm_pretouch_diag.py --steps 4 --warmup 3 --no-cpu-baseline --gemm-detail out.txt
+    PRETOUCH=ab python scripts/gemm_pretouch_diag.py --full --steps 4 --warmup 3 --no-cpu-baseline --gemm-detail out.txt
 """
 import os
 import sys

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 export YAT_SERIAL=1
 PASSES="${1:-sq fetch write}"
 [ $# -gt 0 ] && shift
-ARGS="${*:-bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-gemm-timer}"
+ARGS="${*:-bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-gemm-timer}"
 run() { # name counters...
   name=$1; shift
   timeout -k 10 400 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d gpurun_out/pmc_$name -o pmc -- python3 $ARGS > gpurun_out/pmc_$name.json 2> gpurun_out/pmc_$name.err

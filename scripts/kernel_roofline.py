@@ -13,6 +13,8 @@ import re
 import sys
 
 path = sys.argv[1]
+# default: the profserial run of scripts/gpu_round.sh, bench.py --full --steps 5 --warmup 2 = 2 warm-up + 5 timed + 4 host-enqueue
+# steps (one per bucket, run by --full after the timed region)
 steps = float(sys.argv[2]) if len(sys.argv) > 2 else 11.0
 M, D, Hc, NP = 8048.0, 2240.0, 5600.0, 1.6045e9
 T = 1300.0            # packed text rows per batch (mean)
