@@ -438,6 +438,44 @@ int yat_adamw_step(int64_t n, void* param, void* grad, void* exp_avg, void* exp_
                    void* ema_shadow, double ema_decay, int background, yat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * DC-AE decoder (diffusers AutoencoderDC, decoder only): the VAE decode of the validation images,
+ *   vae.decode(latent / vae.config.scaling_factor) -> image_processor.postprocess   train_sana.py:153-157
+ * with the VAE in bf16 (train_sana.py:60).  Activations are NHWC bf16; every call only enqueues work.  The 1x1 convs and
+ * Linears of the decoder run on yat_gemm_bf16_ex, its GLUMBConv middle on yat_dwconv_glu_fwd and its ReLU linear attention
+ * on yat_linear_attn_fwd (yat_amd/dcae.py); the entry points below are what those do not cover.
+ *
+ * yat_dcae_conv3x3: nn.Conv2d(Cin, Cout, 3, padding=1) -- ResBlock conv1 / conv2, DCUpBlock2d.conv, Decoder.conv_in /
+ *   conv_out.  x: [B, H/2, W/2, Cin] with upsample = 1 (F.interpolate(scale_factor=2, mode='nearest') applied in the
+ *   address math), else [B, H, W, Cin]; w: [Cout, 3, 3, Cin] (the torch weight [Cout, Cin, 3, 3] permuted); bias [Cout]
+ *   or NULL; y: [B, H, W, Cout].  Epilogue order, each step rounded to bf16 as the bf16 module outputs are:
+ *     conv + bias -> silu (silu = 1) -> + shortcut -> + residual ([B, H, W, Cout] or NULL)
+ *   shortcut_mode 0: none; 1: repeat_interleave(shortcut, Cout / shortcut_channels, dim=C), shortcut [B, H, W, sc]
+ *   (Decoder.conv_in's in_shortcut); 2: pixel_shuffle(repeat_interleave(shortcut, r, dim=C), 2), r = 4 Cout /
+ *   shortcut_channels, shortcut [B, H/2, W/2, sc] (DCUpBlock2d's shortcut).  Cin % 8 == 0; Cout % 4 == 0 (MFMA implicit
+ *   GEMM) or Cout <= 4 (direct kernel for the RGB conv_out: no shortcut, Cout * 9 * Cin * 2 <= 64 KiB; out_nchw = 1
+ *   writes y as [B, Cout, H, W]); the input must be < 2 GiB.
+ * yat_dcae_msla_aggregate: SanaMultiscaleAttentionProjection (to_qkv_multiscale.0): depthwise 5x5 conv over C3 channels
+ *   (pad 2, no bias; w_dw [C3, 25]), rounded to bf16, then the grouped 1x1 conv with C3 / 32 groups of 32 -> 32 (no bias;
+ *   w_pw [C3, 32]: row o holds the weights of output channel o over its group's 32 inputs).  qkv, out: [B, H, W, C3],
+ *   C3 % 32 == 0.
+ * yat_dcae_rmsnorm_bias: diffusers RMSNorm(D, eps, elementwise_affine=True, bias=True) as the bf16 VAE rounds it:
+ *   y = bf16(bf16(bf16(x * rsqrt(mean(x^2) + eps)) * w) + b)  (statistics in fp32; b may be NULL),
+ *   then y = bf16(y + residual) if residual != NULL (ResBlock / EfficientViTBlock), then y = max(y, 0) if relu
+ *   (Decoder.norm_out -> conv_act).  x, residual, y: [M, D], D % 8 == 0; y may alias residual.  yat_rmsnorm_fwd (caption
+ *   norm, no bias) is a separate entry point and unchanged.
+ * yat_dcae_image_to_uint8: VaeImageProcessor.postprocess + numpy_to_pil of the decoded image, elementwise over n values:
+ *   p = clamp(bf16(bf16(x * 0.5) + 0.5), 0, 1);  out = uint8(round_half_even(float(p) * 255)).
+ * ------------------------------------------------------------------------------------------ */
+int yat_dcae_conv3x3(int B, int H, int W, int Cin, int Cout, int upsample, int silu, const void* x, const void* w,
+                     const void* bias, int shortcut_mode, const void* shortcut, int shortcut_channels, const void* residual,
+                     int out_nchw, void* y, yat_stream_t stream);
+int yat_dcae_msla_aggregate(int B, int H, int W, int C3, const void* qkv, const void* w_dw, const void* w_pw, void* out,
+                            yat_stream_t stream);
+int yat_dcae_rmsnorm_bias(int M, int D, float eps, const void* x, const void* w, const void* b, const void* residual,
+                          int relu, void* y, yat_stream_t stream);
+int yat_dcae_image_to_uint8(int64_t n, const void* x, void* out, yat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * launch plans: replay a recorded sequence of entry-point calls and stream / event operations in ONE call.
  * A training step over the same buffers issues the same ~900 launches and ~500 stream / event operations every time
  * (yat_amd/flat.py records them); replaying the list from C costs ~1 us per entry instead of a host-language call each.

@@ -8,7 +8,8 @@ train_sana.py:221-237), driving the MI355X-native hot path.
 ``pretrained_model_path`` (or ``pretrained_pipe_path``/transformer) must be a LOCAL diffusers directory
 (config.json + diffusion_pytorch_model.safetensors); with neither present the 1.6B architecture is random-initialised
 (there is no network here).  Feature extraction (VAE / text encoder, ``extract_features`` / ``compute_features``) is outside the hot-path scope:
-training consumes cached-feature shards; validation samples latents from cached prompt embeddings (no VAE decode).
+training consumes cached-feature shards; validation samples latents from cached prompt embeddings and, when
+``<pretrained_pipe_path>/vae`` holds the DC-AE, decodes them to images on the HIP decoder (yat_amd/dcae.py).
 """
 import argparse
 import json
@@ -19,6 +20,7 @@ import torch
 from yat_amd.common.training_parameters_reader import TrainingParameters
 from yat_amd.common.trainer import Model
 from yat_amd.common.aspect_ratios import table_for_resolution
+from yat_amd.dcae import find_vae_dir
 from yat_amd.recipe import SanaRecipe
 from yat_amd.sana import SanaConfig, SanaTransformer2DModelHIP
 from yat_amd.scheduler import FlowMatchSchedule
@@ -46,6 +48,8 @@ class SanaModel(Model):
         self.model.enable_gradient_checkpointing()                                             # :63 (no-op here)
         self.recipe = SanaRecipe(self.model, self.scheduler, pad_to=512, device=dev)
         self.pipe = None
+        self.vae_dir = find_vae_dir(params.pretrained_pipe_path)                              # :47-60 (decoder only)
+        self.vae = None                                                                        # built at the first validate()
 
     def extract_latents(self, images):
         raise NotImplementedError("VAE encoding is outside the hot-path scope; train from cached-feature shards")
@@ -58,7 +62,10 @@ class SanaModel(Model):
         generator seeded 42 (:108).  The text encoder and the VAE are outside this build's scope, so the prompt embeddings
         come from a cached file (``validation_embeds.pt`` next to the shards or in the cwd: a list of
         (prompt_embeds [1,T,C], mask [1,T], negative_embeds, negative_mask) tuples as ``pipe.encode_prompt`` returns them)
-        and the result is the latents (``output_type='latent'``), stored under models/<step>/."""
+        and the result is the latents (``output_type='latent'``), stored under models/<step>/.  With a DC-AE in
+        ``<pretrained_pipe_path>/vae`` the last third runs too: each latent is decoded on the HIP decoder
+        (``vae.decode(latent / scaling_factor)`` -> ``postprocess``, :153-156), logged as ``validation/{idx}/{prompt}``
+        (:157) and written to models/<step>/validation_{idx}.png."""
         from yat_amd.sampler import sample_latents
         cands = [os.path.join(os.path.dirname(p), "validation_embeds.pt") for p in (self.params.local_shard_paths or [])]
         path = next((c for c in cands + ["validation_embeds.pt"] if os.path.isfile(c)), None)
@@ -78,7 +85,23 @@ class SanaModel(Model):
                 x = lat[0, :3].float()
                 x = (x - x.amin()) / (x.amax() - x.amin()).clamp_min(1e-6)
                 self.logger.add_image(f"validation_latents/{idx}", x, self.global_step)
+        if self.vae_dir is not None:
+            self._decode_validation(out)
         return out
+
+    def _decode_validation(self, latents):
+        from yat_amd.common.tb_writer import encode_png
+        from yat_amd.dcae import AutoencoderDCDecoderHIP
+        if self.vae is None:
+            self.vae = AutoencoderDCDecoderHIP.from_pretrained(self.vae_dir, device=self.accelerator.device)
+        prompts = list(self.params.validation_prompts or [])
+        for idx, lat in enumerate(latents):
+            img = self.vae.to_uint8(self.vae.decode(lat))[0].cpu()
+            with open(f"models/{self.global_step}/validation_{idx}.png", "wb") as f:
+                f.write(encode_png(img))
+            if self.logger is not None:
+                tag = f"validation/{idx}/{prompts[idx]}" if idx < len(prompts) else f"validation/{idx}"
+                self.logger.add_image(tag, img, self.global_step)
 
     def optimize(self, ratio, latents, embeddings, repa_tokens, generator: torch.Generator = None):
         """train_sana.py:163-219 on the HIP path.  With gradients enabled (the training call, common/trainer.py:337) the step

@@ -802,3 +802,37 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, clip_coef, lr, beta1, beta2, ep
                                beta2, eps, weight_decay, step, int(zero_grad), _p(ema_shadow), ema_decay, int(background),
                                _stream())
     _l.check(rc, "yat_adamw_step")
+
+
+# ----------------------------------------------------------------------------------------------- DC-AE decoder (yat_amd/dcae.py)
+def dcae_conv3x3(x, w, y, B, H, W, Cin, Cout, bias=None, upsample=False, silu=False, shortcut_mode=0, shortcut=None,
+                 shortcut_channels=0, residual=None, out_nchw=False):
+    """3x3 conv, pad 1, NHWC (include/yat_hip.h yat_dcae_conv3x3); w is [Cout, 3, 3, Cin]."""
+    _chk_bf16(x, w, y, bias, shortcut, residual)
+    rc = _lib().yat_dcae_conv3x3(B, H, W, Cin, Cout, int(upsample), int(silu), _p(x), _p(w), _p(bias), int(shortcut_mode),
+                                 _p(shortcut), int(shortcut_channels), _p(residual), int(out_nchw), _p(y), _stream())
+    _l.check(rc, "yat_dcae_conv3x3")
+    return y
+
+
+def dcae_msla_aggregate(qkv, w_dw, w_pw, out, B, H, W, C3):
+    _chk_bf16(qkv, w_dw, w_pw, out)
+    rc = _lib().yat_dcae_msla_aggregate(B, H, W, C3, _p(qkv), _p(w_dw), _p(w_pw), _p(out), _stream())
+    _l.check(rc, "yat_dcae_msla_aggregate")
+    return out
+
+
+def dcae_rmsnorm_bias(x2d, w, b, y, eps=1e-5, residual=None, relu=False):
+    _chk_bf16(x2d, w, b, y, residual)
+    M, D = x2d.shape
+    rc = _lib().yat_dcae_rmsnorm_bias(M, D, eps, _p(x2d), _p(w), _p(b), _p(residual), int(relu), _p(y), _stream())
+    _l.check(rc, "yat_dcae_rmsnorm_bias")
+    return y
+
+
+def dcae_image_to_uint8(x, out=None):
+    _chk_bf16(x)
+    out = out if out is not None else torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    rc = _lib().yat_dcae_image_to_uint8(x.numel(), _p(x), _p(out), _stream())
+    _l.check(rc, "yat_dcae_image_to_uint8")
+    return out
