@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void gradnorm_final_kernel(int nseg, const int
     if (threadIdx.x == 0) {
         const float total = rbf(sqrtf(red[0] + red[1] + red[2] + red[3]));
         float coef = rbf(max_norm / rbf(total + 1e-6f));
-        coef = fminf(coef, 1.0f);
+        coef = coef > 1.0f ? 1.0f : coef;   // torch.clamp(max=1.0) keeps a NaN (fminf would give 1)
         norm_out[0] = total;
         clip_coef[0] = coef;
     }
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void gradnorm_pieces_final_kernel(int ntensor,
     if (threadIdx.x == 0) {
         const float total = rbf(sqrtf(red[0] + red[1] + red[2] + red[3]));
         float coef = rbf(max_norm / rbf(total + 1e-6f));
-        coef = fminf(coef, 1.0f);
+        coef = coef > 1.0f ? 1.0f : coef;   // torch.clamp(max=1.0) keeps a NaN (fminf would give 1)
         norm_out[0] = total;
         clip_coef[0] = coef;
     }
