@@ -476,6 +476,35 @@ int yat_dcae_rmsnorm_bias(int M, int D, float eps, const void* x, const void* w,
 int yat_dcae_image_to_uint8(int64_t n, const void* x, void* out, yat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * AutoencoderKL decoder (diffusers AutoencoderKL, decoder only): the VAE decode of the PixArt-Sigma and SD3.5 validation
+ * images,  vae.decode(latent / vae.config.scaling_factor) -> image_processor.postprocess   train_pixart_sigma.py:137-144,
+ * train_sd35.py:150-156, with the VAE in bf16.  Activations are NHWC bf16; every call only enqueues work.  The 3x3 convs run
+ * on yat_dcae_conv3x3, post_quant_conv / the 1x1 conv_shortcut / to_q|to_k|to_v / to_out.0 on yat_gemm_bf16_ex (bias
+ * epilogue; to_out.0 with the residual epilogue, which rounds the Linear output before adding, as diffusers does) and the
+ * postprocess on yat_dcae_image_to_uint8 (yat_amd/autoencoder_kl.py); the entry points below are what those do not cover.
+ *
+ * yat_vae_groupnorm: nn.GroupNorm(G, C, eps, affine=True) of the bf16 module (ResnetBlock2D.norm1 / norm2, Attention.group_norm,
+ *   Decoder.conv_norm_out), optionally followed by the SiLU module (silu = 1):
+ *     mean, var = statistics of image b, group g over its HW * C / G values in fp32 (biased variance);
+ *     y = bf16((x - mean) * rsqrt(var + eps) * w + b)  (fp32 arithmetic, one rounding);  silu = 1: y = bf16(silu(y)).
+ *   x, y: [B, HW, C] (y may alias x); w, b: [C] bf16.  C % G == 0, C % 8 == 0, C <= 2048, any HW; all four pointers 16-byte
+ *   aligned.  The statistics are a split reduction: fixed-size slab partials of shifted sums, combined in a fixed order --
+ *   no atomics, two calls on the same input are bit-identical.  workspace: caller-owned, 16-byte aligned, >=
+ *   yat_vae_groupnorm_workspace_bytes(B, HW, C, G) bytes; NULL is YAT_EINVAL.
+ * yat_vae_attn_fwd: F.scaled_dot_product_attention(q, k, v) with ONE head of dh channels, no mask, scale dh^-0.5 (the
+ *   UNetMidBlock2D Attention: heads = 1, head dim = the mid-block width).  q, k, v: [B * N, >= dh] bf16 with row stride ld
+ *   (column blocks of the fused [B * N, 3 dh] to_q|to_k|to_v output); out: [B * N, >= dh] with row stride ldo.  Flash-style:
+ *   scores and the online softmax in fp32, the probabilities rounded to bf16 for the P V product, fp32 accumulation, out =
+ *   bf16(O / rowsum) with rowsum the fp32 sum of the same rounded probabilities.  dh in {64, 512} (512: every SD-family KL VAE; 64: small test VAEs), other dh YAT_EINVAL; ld, ldo
+ *   multiples of 8, pointers 16-byte aligned, B * N * ld < 2^30.  Deterministic (no atomics).
+ * ------------------------------------------------------------------------------------------ */
+uint64_t yat_vae_groupnorm_workspace_bytes(int B, int HW, int C, int G);
+int yat_vae_groupnorm(int B, int HW, int C, int G, float eps, const void* x, const void* w, const void* b, int silu, void* y,
+                      void* workspace, yat_stream_t stream);
+int yat_vae_attn_fwd(int B, int N, int dh, const void* q, const void* k, const void* v, int ld, void* out, int ldo,
+                     yat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * launch plans: replay a recorded sequence of entry-point calls and stream / event operations in ONE call.
  * A training step over the same buffers issues the same ~900 launches and ~500 stream / event operations every time
  * (yat_amd/flat.py records them); replaying the list from C costs ~1 us per entry instead of a host-language call each.

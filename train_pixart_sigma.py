@@ -6,9 +6,9 @@ train_pixart_sigma.py:187-198), driving the MI355X-native path (BASELINE config 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train_pixart_sigma.py --config config.yaml
 
 ``pretrained_model_path`` (or ``pretrained_pipe_path``/transformer) must be a LOCAL diffusers directory; with neither the
-PixArt-Sigma-XL-2 architecture is random-initialised (no network here).  VAE / T5 feature extraction and the validation
-pipeline (PAG + DPM-Solver sampling + VAE decode, :78-149) are outside the hot-path scope: training consumes cached-feature
-shards and ``validate()`` is a no-op that leaves the checkpoint cadence intact.
+PixArt-Sigma-XL-2 architecture is random-initialised (no network here).  VAE / T5 feature extraction is outside the hot-path
+scope: training consumes cached-feature shards; validation samples latents from cached prompt embeddings and, when
+``<pretrained_pipe_path>/vae`` holds the AutoencoderKL, decodes them to images on the HIP decoder (yat_amd/autoencoder_kl.py).
 
 Reference quirk: ``PixartSigmaTrainer.optimize(self, latents, embeddings)`` (:151) still has the two-argument signature
 while ``Model.run`` calls ``optimize(ratio, latents, embeddings, repa_features, generator)`` (common/trainer.py:337) -- at
@@ -23,8 +23,10 @@ import torch
 
 from yat_amd.common.training_parameters_reader import TrainingParameters
 from yat_amd.common.trainer import Model
+from yat_amd.autoencoder_kl import decode_validation, load_vae_decoder
 from yat_amd.common.aspect_ratios import table_for_resolution
 from yat_amd.pixart import PixArtConfig, PixArtTransformer2DModelHIP
+from yat_amd.dcae import find_vae_dir
 from yat_amd.recipe import PixArtRecipe
 from yat_amd.scheduler import DDPMSchedule
 
@@ -58,6 +60,8 @@ class PixartSigmaTrainer(Model):
         self.aspect_ratios = table_for_resolution(self.model.config.sample_size * vae_compression)
         self.recipe = PixArtRecipe(self.model, self.scheduler, pad_to=300, device=dev)
         self.pipe = None
+        self.vae_dir = find_vae_dir(params.pretrained_pipe_path)                              # decoder only
+        self.vae = None                                                                        # built at the first validate()
 
     def extract_latents(self, images):
         raise NotImplementedError("VAE encoding is outside the hot-path scope; train from cached-feature shards")
@@ -71,7 +75,10 @@ class PixartSigmaTrainer(Model):
         (:94).  The T5 encoder and the VAE are outside this build's scope, so the prompt embeddings come from a cached file
         (``validation_embeds.pt`` next to the shards or in the cwd: a list of (prompt_embeds [1,T,C], mask [1,T],
         negative_embeds, negative_mask) tuples as ``pipe.encode_prompt`` returns them, :100-108) and the result is the latents
-        (``output_type='latent'``), stored under models/<step>/ with a three-channel preview for the logger (:143)."""
+        (``output_type='latent'``), stored under models/<step>/ with a three-channel preview for the logger.  With an
+        AutoencoderKL in ``<pretrained_pipe_path>/vae`` the last third runs too (:137-144): each latent is decoded on the HIP
+        decoder (``vae.decode(latent / scaling_factor)`` -> ``postprocess``), logged as ``validation/{idx}/{prompt}`` and
+        written to models/<step>/validation_{idx}.png; the decoder is built at the first call."""
         from yat_amd.sampler import sample_latents_pixart
         cands = [os.path.join(os.path.dirname(p), "validation_embeds.pt") for p in (self.params.local_shard_paths or [])]
         path = next((c for c in cands + ["validation_embeds.pt"] if os.path.isfile(c)), None)
@@ -91,6 +98,10 @@ class PixartSigmaTrainer(Model):
                 x = lat[0, :3].float()
                 x = (x - x.amin()) / (x.amax() - x.amin()).clamp_min(1e-6)
                 self.logger.add_image(f"validation_latents/{idx}", x, self.global_step)
+        if self.vae_dir is not None:
+            if self.vae is None:
+                self.vae = load_vae_decoder(self.vae_dir, device=self.accelerator.device)
+            decode_validation(self.vae, out, self.params.validation_prompts, self.global_step, self.logger)
         return out
 
     def optimize(self, ratio, latents, embeddings, repa_tokens=None, generator: torch.Generator = None):

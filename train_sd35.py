@@ -6,9 +6,10 @@ driving the MI355X-native MMDiT path (BASELINE config 4).
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train_sd35.py --config config.yaml
 
 ``pretrained_model_path`` (or ``pretrained_pipe_path``/transformer) must be a LOCAL diffusers directory; with neither the
-SD3.5-Medium architecture is random-initialised (no network here).  The three text encoders, the VAE and the validation
-pipeline (:94-163) are outside the hot-path scope: training consumes cached-feature shards whose samples carry the prompt
-embeddings (``emb.pt`` [333, 4096]) and the pooled projection (``pooled.pt`` [2048]).
+SD3.5-Medium architecture is random-initialised (no network here).  The three text encoders and the VAE encoder are outside
+the hot-path scope: training consumes cached-feature shards whose samples carry the prompt embeddings (``emb.pt`` [333,
+4096]) and the pooled projection (``pooled.pt`` [2048]); validation decodes its latents on the HIP AutoencoderKL decoder
+(yat_amd/autoencoder_kl.py) when ``<pretrained_pipe_path>/vae`` holds the VAE.
 
 Reference quirks: ``SD35Trainer.optimize(self, model, batch)`` (:165) has a pre-refactor signature with a
 ``(latents, embeddings, pooled_projections)`` batch no sampler produces any more, while ``Model.run`` calls
@@ -25,7 +26,9 @@ import torch
 
 from yat_amd.common.training_parameters_reader import TrainingParameters
 from yat_amd.common.trainer import Model
+from yat_amd.autoencoder_kl import decode_validation, load_vae_decoder
 from yat_amd.common.aspect_ratios import ASPECT_RATIO_1024_BIN
+from yat_amd.dcae import find_vae_dir
 from yat_amd.recipe import SD3Recipe
 from yat_amd.scheduler import FlowMatchSchedule
 from yat_amd.sd3 import SD3Config, SD3Transformer2DModelHIP
@@ -52,6 +55,8 @@ class SD35Trainer(Model):
         self.aspect_ratios = ASPECT_RATIO_1024_BIN                                              # :55
         self.recipe = SD3Recipe(self.model, self.scheduler, device=dev)
         self.pipe = None
+        self.vae_dir = find_vae_dir(params.pretrained_pipe_path)                              # decoder only
+        self.vae = None                                                                        # built at the first validate()
 
     def extract_latents(self, images):
         raise NotImplementedError("VAE encoding is outside the hot-path scope; train from cached-feature shards")
@@ -80,7 +85,11 @@ class SD35Trainer(Model):
         embeddings come from a cached file (``validation_embeds.pt`` next to the shards or in the cwd: a list of
         (prompt_embeds [1,T,C], negative_prompt_embeds, pooled_prompt_embeds [1,P], negative_pooled_prompt_embeds) tuples as
         ``pipe.encode_prompt`` returns them, :116-118) and the result is the latents (``output_type='latent'``), stored
-        under models/<step>/ with a three-channel preview for the logger in place of the decoded image (:154)."""
+        under models/<step>/ with a three-channel preview for the logger.  With an AutoencoderKL in
+        ``<pretrained_pipe_path>/vae`` each latent is then decoded on the HIP decoder, logged as ``validation/{idx}/{prompt}``
+        and written to models/<step>/validation_{idx}.png (:150-156).  As in the reference the decoder's argument is
+        ``latent / scaling_factor`` WITHOUT ``+ shift_factor`` (:155; diffusers' own SD3 pipeline adds it): this keeps the
+        reference's outward contract (yat_amd/autoencoder_kl.py ``pre_scale``)."""
         from yat_amd.sampler import sample_latents_sd3
         cands = [os.path.join(os.path.dirname(p), "validation_embeds.pt") for p in (self.params.local_shard_paths or [])]
         path = next((c for c in cands + ["validation_embeds.pt"] if os.path.isfile(c)), None)
@@ -100,6 +109,10 @@ class SD35Trainer(Model):
                 x = lat[0, :3].float()
                 x = (x - x.amin()) / (x.amax() - x.amin()).clamp_min(1e-6)
                 self.logger.add_image(f"validation_latents/{idx}", x, self.global_step)
+        if self.vae_dir is not None:
+            if self.vae is None:
+                self.vae = load_vae_decoder(self.vae_dir, device=self.accelerator.device)
+            decode_validation(self.vae, out, self.params.validation_prompts, self.global_step, self.logger)
         return out
 
     def optimize(self, ratio, latents, embeddings, repa_tokens=None, generator: torch.Generator = None):

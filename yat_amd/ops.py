@@ -836,3 +836,25 @@ def dcae_image_to_uint8(x, out=None):
     rc = _lib().yat_dcae_image_to_uint8(x.numel(), _p(x), _p(out), _stream())
     _l.check(rc, "yat_dcae_image_to_uint8")
     return out
+
+
+# --------------------------------------------------------------------------------- AutoencoderKL decoder (yat_amd/autoencoder_kl.py)
+def vae_groupnorm_workspace_bytes(B, HW, C, G):
+    return int(_lib().yat_vae_groupnorm_workspace_bytes(B, HW, C, G))
+
+
+def vae_groupnorm(x, w, b, y, B, HW, C, G, workspace, eps=1e-6, silu=False):
+    """nn.GroupNorm(G, C, eps) (+ SiLU) over NHWC [B, HW, C] (include/yat_hip.h yat_vae_groupnorm); y may be x."""
+    _chk_bf16(x, w, b, y)
+    rc = _lib().yat_vae_groupnorm(B, HW, C, G, float(eps), _p(x), _p(w), _p(b), int(silu), _p(y), _p(workspace), _stream())
+    _l.check(rc, "yat_vae_groupnorm")
+    return y
+
+
+def vae_attn_fwd(q, k, v, out, B, N, dh, ld, ldo=None):
+    """Single-head SDPA, scale dh^-0.5, no mask (yat_vae_attn_fwd); q / k / v are column views of a [B*N, ld] matrix."""
+    _chk_bf16(q, k, v, out)
+    rc = _lib().yat_vae_attn_fwd(B, N, dh, _p(q), _p(k), _p(v), int(ld), _p(out), int(ldo if ldo is not None else dh),
+                                 _stream())
+    _l.check(rc, "yat_vae_attn_fwd")
+    return out
