@@ -476,6 +476,34 @@ int yat_dcae_rmsnorm_bias(int M, int D, float eps, const void* x, const void* w,
 int yat_dcae_image_to_uint8(int64_t n, const void* x, void* out, yat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * DC-AE encoder (diffusers AutoencoderDC, encoder only): the VAE encode of feature extraction,
+ *   vae.encode(images).latent.to(bf16) * vae.config.scaling_factor                  train_sana.py:78-82
+ * with the VAE in bf16.  Activations are NHWC bf16; every call only enqueues work.  ResBlock / EfficientViTBlock and the
+ * stride-1 convs run on the decoder's entry points above (yat_amd/dcae_encoder.py); the entry points below are what those
+ * do not cover.  Weights w: [Cout, 3, 3, Cin] as for yat_dcae_conv3x3; bias [Cout] or NULL; Cin % 8 == 0, Cout % 4 == 0;
+ * the input must be < 2 GiB.  Epilogue of both convs, each step rounded to bf16 as the bf16 module rounds it:
+ *     c = bf16(conv + bias);  s = bf16(fp32 mean of the g shortcut values);  y = bf16(c + s)      (shortcut = 1)
+ *     y = bf16(conv + bias)                                                                        (shortcut = 0)
+ *
+ * yat_dcae_conv3x3_down: DCDownBlock2d in its "Conv" form: nn.Conv2d(Cin, Cout, 3, stride=2, padding=1) plus the shortcut
+ *   pixel_unshuffle(x, 2).unflatten(1, (-1, g)).mean(dim=2), g = 4 Cin / Cout (shortcut = 1 needs 4 Cin % Cout == 0):
+ *   output channel o averages unshuffled channels u = o g .. o g + g - 1, and unshuffled channel u is input channel u / 4
+ *   at offset (dy, dx) = ((u % 4) / 2, u % 2) of the 2 x 2 input block of the output pixel.
+ *   x: [B, H, W, Cin], H and W even; y: [B, H/2, W/2, Cout].
+ * yat_dcae_conv3x3_mean: Encoder.conv_out: nn.Conv2d(Cin, Cout, 3, padding=1) plus x.unflatten(1, (-1, g)).mean(dim=2),
+ *   g = Cin / Cout (shortcut = 1 needs Cin % Cout == 0).  x: [B, H, W, Cin]; y: [B, H, W, Cout].
+ * yat_dcae_image_from_uint8: torchvision ToTensor -> Normalize(0.5, 0.5) -> .to(bfloat16) of an RGB image, padded to the 8
+ *   input channels the MFMA conv_in reads:  x: [npix, 3] uint8 -> out: [npix, 8] bf16, out[p, c] = table[x[p, c]] for
+ *   c < 3 and 0 for c >= 3.  table: 256 bf16 values on the device, filled by the host with bf16(((u / 255) - 0.5) / 0.5)
+ *   in fp32 IEEE arithmetic (u * (2 / 255) - 1 is not the same for every u).  out 16-byte aligned, npix < 2^28.
+ * ------------------------------------------------------------------------------------------ */
+int yat_dcae_conv3x3_down(int B, int H, int W, int Cin, int Cout, const void* x, const void* w, const void* bias,
+                          int shortcut, void* y, yat_stream_t stream);
+int yat_dcae_conv3x3_mean(int B, int H, int W, int Cin, int Cout, const void* x, const void* w, const void* bias,
+                          int shortcut, void* y, yat_stream_t stream);
+int yat_dcae_image_from_uint8(int64_t npix, const void* x, const void* table, void* out, yat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * AutoencoderKL decoder (diffusers AutoencoderKL, decoder only): the VAE decode of the PixArt-Sigma and SD3.5 validation
  * images,  vae.decode(latent / vae.config.scaling_factor) -> image_processor.postprocess   train_pixart_sigma.py:137-144,
  * train_sd35.py:150-156, with the VAE in bf16.  Activations are NHWC bf16; every call only enqueues work.  The 3x3 convs run

@@ -7,8 +7,9 @@ train_sana.py:221-237), driving the MI355X-native hot path.
 
 ``pretrained_model_path`` (or ``pretrained_pipe_path``/transformer) must be a LOCAL diffusers directory
 (config.json + diffusion_pytorch_model.safetensors); with neither present the 1.6B architecture is random-initialised
-(there is no network here).  Feature extraction (VAE / text encoder, ``extract_features`` / ``compute_features``) is outside the hot-path scope:
-training consumes cached-feature shards; validation samples latents from cached prompt embeddings and, when
+(there is no network here).  Text encoding and the ``extract_features`` / ``compute_features`` loop are outside the hot-path
+scope: training consumes cached-feature shards (``python -m yat_amd.extract_latents`` makes their latents on the HIP DC-AE
+encoder, which ``extract_latents`` also uses); validation samples latents from cached prompt embeddings and, when
 ``<pretrained_pipe_path>/vae`` holds the DC-AE, decodes them to images on the HIP decoder (yat_amd/dcae.py).
 """
 import argparse
@@ -50,9 +51,19 @@ class SanaModel(Model):
         self.pipe = None
         self.vae_dir = find_vae_dir(params.pretrained_pipe_path)                              # :47-60 (decoder only)
         self.vae = None                                                                        # built at the first validate()
+        self.vae_encoder = None                                                                # built at the first extract_latents()
 
     def extract_latents(self, images):
-        raise NotImplementedError("VAE encoding is outside the hot-path scope; train from cached-feature shards")
+        """train_sana.py:78-82 on the HIP DC-AE encoder (yat_amd/dcae_encoder.py), built from ``<pretrained_pipe_path>/vae``
+        at the first call: ``vae.encode(images.to(bf16)).latent.to(bf16) * scaling_factor``."""
+        if self.vae_dir is None:
+            want = os.path.join(self.params.pretrained_pipe_path or "<pretrained_pipe_path>", "vae")
+            raise NotImplementedError(f"VAE encoding needs the DC-AE in {want!r} (config.json + safetensors); without it, "
+                                      "train from cached-feature shards")
+        if self.vae_encoder is None:
+            from yat_amd.dcae_encoder import AutoencoderDCEncoderHIP
+            self.vae_encoder = AutoencoderDCEncoderHIP.from_pretrained(self.vae_dir, device=self.accelerator.device)
+        return self.vae_encoder.encode(images)
 
     def extract_embeddings(self, captions):
         raise NotImplementedError("text encoding is outside the hot-path scope; train from cached-feature shards")
@@ -124,6 +135,7 @@ if __name__ == "__main__":
     params = TrainingParameters()
     params.read_yaml(args.config)
     if params.extract_features:
-        raise SystemExit("extract_features (VAE/text-encoder feature extraction) is outside this build's scope")
+        raise SystemExit("extract_features needs the text encoder and the R2 transport, which are outside this build's scope; "
+                         "`python -m yat_amd.extract_latents` encodes image files into a shard on the HIP DC-AE encoder")
     trainer = SanaModel(params)
     trainer.run(max_steps=args.max_steps)

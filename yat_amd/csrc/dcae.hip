@@ -9,21 +9,13 @@
 //   msla_aggregate  SanaMultiscaleAttentionProjection: depthwise 5x5 (pad 2) + grouped 1x1 (32 -> 32 per group), one pass.
 //   rmsnorm_bias    diffusers RMSNorm(eps, elementwise_affine, bias) with its bf16 rounding, + residual, + ReLU.
 //   image_to_uint8  VaeImageProcessor.postprocess: (x / 2 + 0.5).clamp(0, 1) in bf16, then numpy's round(x * 255).
-#include "common.hpp"
+#include "dcae_conv.hpp"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------------------- conv3x3
-// 128 x 128 x 64 tile, 4 waves (2 x 2), each wave 64 x 64 = 4 x 4 MFMA 16x16x32 accumulators.  Both operands move
-// HBM -> LDS by LDS-DMA (16 B per lane), double-buffered, one barrier per K-tile.  The A operand (im2col rows) is never
-// materialised: every lane computes, per 16-B chunk, the tap and input channel of its K slice and the input pixel of
-// its row; taps outside the image (zero padding), rows past M and K past 9 Cin are predicated to the buffer descriptor's
-// out-of-range offset, which the hardware returns as zeros.  Cin % 8 == 0, so a 16-B chunk never straddles two taps.
-// LDS images are lane-linear with the XOR swizzle applied to the source chunk (common.hpp swz128) and undone on the read.
-constexpr int CBM = 128, CBN = 128, CBK = 64;
-constexpr int CSTAGE = (CBM * CBK + CBN * CBK) * 2;  // 32 KiB
-constexpr int CLDS = 2 * CSTAGE;                     // 64 KiB -> 2 workgroups / CU
-
+// The tile, its B operand, fragment reads and K loop are dcae_conv.hpp (shared with the encoder convs, dcae_enc.hip); this
+// file adds the decoder's A-operand address math (optional nearest x2 upsample) and its epilogue.
 struct ConvP {
     const bf16_t* x;      // [B, Hin, Win, Cin]
     const bf16_t* w;      // [Cout, 9 * Cin]
@@ -68,25 +60,6 @@ __device__ __forceinline__ void conv_stage_a(const ConvP& p, __amdgpu_buffer_rsr
     }
 }
 
-__device__ __forceinline__ void conv_stage_b(const ConvP& p, __amdgpu_buffer_rsrc_t rw, char* lds, int n0, int k0, int wave,
-                                             int lane) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int piece = j * 4 + wave;
-        const int r = piece * 8 + (lane >> 3);
-        const int c = swz128(r, lane & 7);
-        const int gn = n0 + r, gk = k0 + c * 8;
-        const uint32_t voff = (gn < p.Cout && gk < p.K) ? (uint32_t)(((int64_t)gn * p.K + gk) * 2) : YAT_OOB;
-        lds_dma16(rw, (YAT_LDS void*)(lds + piece * 1024), voff);
-    }
-}
-
-__device__ __forceinline__ bf16x8 conv_frag(const char* lds, int idx0, int kk, int lane) {
-    const uint32_t r = idx0 + (lane & 15);
-    const uint32_t c = swz128(r, kk * 4 + (lane >> 4));
-    return lds_read8(lds, r * 128 + c * 16);
-}
-
 // epilogue of 4 consecutive output channels n..n+3 of pixel m:
 // +bias -> bf16 -> [SiLU -> bf16] -> [+ shortcut -> bf16] -> [+ residual -> bf16]
 __device__ __forceinline__ void conv_epilogue(const ConvP& p, float (&v)[4], int m, int n) {
@@ -129,15 +102,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(ConvP p) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave >> 1, wn = wave & 1;
 
-    // XCD-contiguous tile order, N fastest: the Cout / 128 tiles of one pixel band share its input rows in one L2
-    const int nwg = p.nbm * p.nbn;
-    int id;
-    {
-        const int orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-    }
-    const int tm = id / p.nbn, tn = id - tm * p.nbn;
-    const int m0 = tm * CBM, n0 = tn * CBN;
+    int m0, n0;
+    conv_tile_origin(p.nbm, p.nbn, m0, n0);
 
     const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, p.x_bytes);
     const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.w, p.w_bytes);
@@ -163,39 +129,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(ConvP p) {
     }
 
     f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int nt = (p.K + CBK - 1) / CBK;
-    conv_stage_a<TAPU>(p, rx, smem, 0, wave, rb, ry, rxx, cc);
-    conv_stage_b(p, rw, smem + CBM * CBK * 2, n0, 0, wave, lane);
-
-    for (int t = 0; t < nt; ++t) {
-        char* cur = smem + (t & 1) * CSTAGE;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();  // tile t landed for every wave; every wave is done reading the other buffer
-        if (t + 1 < nt) {
-            char* nxt = smem + ((t + 1) & 1) * CSTAGE;
-            conv_stage_a<TAPU>(p, rx, nxt, (t + 1) * CBK, wave, rb, ry, rxx, cc);
-            conv_stage_b(p, rw, nxt + CBM * CBK * 2, n0, (t + 1) * CBK, wave, lane);
-        }
-        const char* la = cur;
-        const char* lb = cur + CBM * CBK * 2;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            bf16x8 af[4], bfr[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = conv_frag(la, wm * 64 + i * 16, kk, lane);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bfr[j] = conv_frag(lb, wn * 64 + j * 16, kk, lane);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(bfr[j], af[i], acc[i][j]);  // D[n][m]
-        }
-    }
+    conv_mainloop(smem, rw, p.Cout, p.K, n0, wave, lane, acc,
+                  [&](char* lds, int k0) { conv_stage_a<TAPU>(p, rx, lds, k0, wave, rb, ry, rxx, cc); });
 
     // lane owns pixel m = .. + (lane & 15) and output channels n = .. + 4 (lane >> 4) + 0..3
 #pragma unroll

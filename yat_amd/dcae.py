@@ -117,6 +117,21 @@ def _validate(cfg: DCAEDecoderConfig) -> None:
         raise NotImplementedError(f"{cfg.out_channels} output channels")
 
 
+def block_keys(p: str, block_type: str, c: int) -> dict:
+    """Keys -> shapes of one ResBlock / EfficientViTBlock of width ``c`` under the diffusers prefix ``p``."""
+    if block_type == RES:
+        return {p + "conv1.weight": (c, c, 3, 3), p + "conv1.bias": (c,), p + "conv2.weight": (c, c, 3, 3),
+                p + "norm.weight": (c,), p + "norm.bias": (c,)}
+    a, g = p + "attn.", p + "conv_out."
+    return {a + "to_q.weight": (c, c), a + "to_k.weight": (c, c), a + "to_v.weight": (c, c),
+            a + "to_qkv_multiscale.0.proj_in.weight": (3 * c, 1, 5, 5),
+            a + "to_qkv_multiscale.0.proj_out.weight": (3 * c, HEAD, 1, 1),
+            a + "to_out.weight": (c, 2 * c), a + "norm_out.weight": (c,), a + "norm_out.bias": (c,),
+            g + "conv_inverted.weight": (8 * c, c, 1, 1), g + "conv_inverted.bias": (8 * c,),
+            g + "conv_depth.weight": (8 * c, 1, 3, 3), g + "conv_depth.bias": (8 * c,),
+            g + "conv_point.weight": (c, 4 * c, 1, 1), g + "norm.weight": (c,), g + "norm.bias": (c,)}
+
+
 def expected_keys(cfg: DCAEDecoderConfig) -> dict:
     """Every ``decoder.*`` key of the diffusers state dict -> its shape."""
     ch, lat, n = cfg.block_out_channels, cfg.latent_channels, cfg.num_stages
@@ -128,20 +143,7 @@ def expected_keys(cfg: DCAEDecoderConfig) -> dict:
             keys[f"decoder.up_blocks.{i}.0.conv.bias"] = (c,)
             j0 = 1
         for j in range(j0, j0 + cfg.layers_per_block[i]):
-            p = f"decoder.up_blocks.{i}.{j}."
-            if cfg.block_types[i] == RES:
-                keys.update({p + "conv1.weight": (c, c, 3, 3), p + "conv1.bias": (c,), p + "conv2.weight": (c, c, 3, 3),
-                             p + "norm.weight": (c,), p + "norm.bias": (c,)})
-            else:
-                a = p + "attn."
-                keys.update({a + "to_q.weight": (c, c), a + "to_k.weight": (c, c), a + "to_v.weight": (c, c),
-                             a + "to_qkv_multiscale.0.proj_in.weight": (3 * c, 1, 5, 5),
-                             a + "to_qkv_multiscale.0.proj_out.weight": (3 * c, HEAD, 1, 1),
-                             a + "to_out.weight": (c, 2 * c), a + "norm_out.weight": (c,), a + "norm_out.bias": (c,)})
-                g = p + "conv_out."
-                keys.update({g + "conv_inverted.weight": (8 * c, c, 1, 1), g + "conv_inverted.bias": (8 * c,),
-                             g + "conv_depth.weight": (8 * c, 1, 3, 3), g + "conv_depth.bias": (8 * c,),
-                             g + "conv_point.weight": (c, 4 * c, 1, 1), g + "norm.weight": (c,), g + "norm.bias": (c,)})
+            keys.update(block_keys(f"decoder.up_blocks.{i}.{j}.", cfg.block_types[i], c))
     keys.update({"decoder.norm_out.weight": (ch[0],), "decoder.norm_out.bias": (ch[0],),
                  "decoder.conv_out.weight": (cfg.out_channels, ch[0], 3, 3), "decoder.conv_out.bias": (cfg.out_channels,)})
     return keys
@@ -179,6 +181,27 @@ def pack_conv3x3(w: torch.Tensor) -> torch.Tensor:
     return w.permute(0, 2, 3, 1).contiguous()
 
 
+def pack_block(b: dict, p: str, q: str, block_type: str, c: int) -> dict:
+    """The re-packed bf16 weights of one block: diffusers prefix ``p`` in ``b`` -> short names under ``q``."""
+    if block_type == RES:
+        return {q + "conv1.w": pack_conv3x3(b[p + "conv1.weight"]), q + "conv1.b": b[p + "conv1.bias"],
+                q + "conv2.w": pack_conv3x3(b[p + "conv2.weight"]),
+                q + "norm.w": b[p + "norm.weight"], q + "norm.b": b[p + "norm.bias"]}
+    a, g = p + "attn.", p + "conv_out."
+    perm = qkv_block_perm(c // HEAD)
+    wcat = torch.cat([b[a + "to_q.weight"], b[a + "to_k.weight"], b[a + "to_v.weight"]], 0)
+    return {
+        q + "qkv.w": permute_blocks(wcat, perm).contiguous(),
+        q + "ms_dw.w": permute_blocks(b[a + "to_qkv_multiscale.0.proj_in.weight"].reshape(3 * c, 25), perm).contiguous(),
+        q + "ms_pw.w": permute_blocks(b[a + "to_qkv_multiscale.0.proj_out.weight"].reshape(3 * c, HEAD), perm).contiguous(),
+        q + "to_out.w": b[a + "to_out.weight"].contiguous(),
+        q + "attn_norm.w": b[a + "norm_out.weight"], q + "attn_norm.b": b[a + "norm_out.bias"],
+        q + "inv.w": b[g + "conv_inverted.weight"].reshape(8 * c, c).contiguous(), q + "inv.b": b[g + "conv_inverted.bias"],
+        q + "dw.w": b[g + "conv_depth.weight"].reshape(8 * c, 9).contiguous(), q + "dw.b": b[g + "conv_depth.bias"],
+        q + "pt.w": b[g + "conv_point.weight"].reshape(c, 4 * c).contiguous(),
+        q + "glu_norm.w": b[g + "norm.weight"], q + "glu_norm.b": b[g + "norm.bias"]}
+
+
 def pack_weights(cfg: DCAEDecoderConfig, sd: dict) -> dict:
     """Strict check + the one-time re-pack (3x3 convs to [Cout, 3, 3, Cin], 1x1 convs to [N, K], fused and block-permuted
     qkv weights) on the host, in bf16.  Keys of the result: the diffusers prefix of each block + a short name."""
@@ -195,25 +218,7 @@ def pack_weights(cfg: DCAEDecoderConfig, sd: dict) -> dict:
             out[f"{i}.up.b"] = b[f"decoder.up_blocks.{i}.0.conv.bias"]
             j0 = 1
         for j in range(j0, j0 + cfg.layers_per_block[i]):
-            p, q = f"decoder.up_blocks.{i}.{j}.", f"{i}.{j}."
-            if cfg.block_types[i] == RES:
-                out.update({q + "conv1.w": pack_conv3x3(b[p + "conv1.weight"]), q + "conv1.b": b[p + "conv1.bias"],
-                            q + "conv2.w": pack_conv3x3(b[p + "conv2.weight"]),
-                            q + "norm.w": b[p + "norm.weight"], q + "norm.b": b[p + "norm.bias"]})
-            else:
-                a, g = p + "attn.", p + "conv_out."
-                perm = qkv_block_perm(c // HEAD)
-                wcat = torch.cat([b[a + "to_q.weight"], b[a + "to_k.weight"], b[a + "to_v.weight"]], 0)
-                out.update({
-                    q + "qkv.w": permute_blocks(wcat, perm).contiguous(),
-                    q + "ms_dw.w": permute_blocks(b[a + "to_qkv_multiscale.0.proj_in.weight"].reshape(3 * c, 25), perm).contiguous(),
-                    q + "ms_pw.w": permute_blocks(b[a + "to_qkv_multiscale.0.proj_out.weight"].reshape(3 * c, HEAD), perm).contiguous(),
-                    q + "to_out.w": b[a + "to_out.weight"].contiguous(),
-                    q + "attn_norm.w": b[a + "norm_out.weight"], q + "attn_norm.b": b[a + "norm_out.bias"],
-                    q + "inv.w": b[g + "conv_inverted.weight"].reshape(8 * c, c).contiguous(), q + "inv.b": b[g + "conv_inverted.bias"],
-                    q + "dw.w": b[g + "conv_depth.weight"].reshape(8 * c, 9).contiguous(), q + "dw.b": b[g + "conv_depth.bias"],
-                    q + "pt.w": b[g + "conv_point.weight"].reshape(c, 4 * c).contiguous(),
-                    q + "glu_norm.w": b[g + "norm.weight"], q + "glu_norm.b": b[g + "norm.bias"]})
+            out.update(pack_block(b, f"decoder.up_blocks.{i}.{j}.", f"{i}.{j}.", cfg.block_types[i], c))
     return out
 
 
@@ -236,6 +241,54 @@ def load_vae_dir(vae_dir: str):
             if k.startswith("decoder."):
                 sd[k] = f.get_tensor(k)
     return cfg, sd
+
+
+def alloc_buffers(sizes, channels, block_types, device) -> dict:
+    """Activation and scratch buffers of one image for stages of ``sizes`` [(h, w)] x ``channels``: two ping-pong
+    activations, the blocks' temporaries (t1, t2; s, g, ws for the EfficientViT stages)."""
+    from . import ops
+    act = max(hh * ww * c for (hh, ww), c in zip(sizes, channels))
+    evit = [(hh * ww, c) for (hh, ww), c, t in zip(sizes, channels, block_types) if t == EVIT]
+    big = max([npx * 8 * c for npx, c in evit], default=0)
+    mid = max([npx * 4 * c for npx, c in evit], default=0)
+    ws = max([ops.linear_attn_workspace_bytes(1, npx, c // HEAD) for npx, c in evit], default=0)
+    e = lambda k: torch.empty(max(k, 1), dtype=BF16, device=device)  # noqa: E731
+    return {"xa": e(act), "xb": e(act), "t1": e(act), "t2": e(act), "s": e(big), "g": e(mid),
+            "ws": torch.empty(max(ws, 16), dtype=torch.uint8, device=device)}
+
+
+# ---------------------------------------------------------------------------- blocks (shared with yat_amd/dcae_encoder.py)
+def res_block(w, q, x, hh, ww, c, bf):
+    """ResBlock ``q`` in place on x ([hh * ww * c] NHWC) through the scratch buffers ``bf``; ``w``: the packed weights."""
+    from . import ops
+    t1, t2 = bf["t1"][:hh * ww * c], bf["t2"][:hh * ww * c]
+    ops.dcae_conv3x3(x, w[q + "conv1.w"], t1, 1, hh, ww, c, c, bias=w[q + "conv1.b"], silu=True)
+    ops.dcae_conv3x3(t1, w[q + "conv2.w"], t2, 1, hh, ww, c, c)
+    x2 = x.view(hh * ww, c)
+    ops.dcae_rmsnorm_bias(t2.view(hh * ww, c), w[q + "norm.w"], w[q + "norm.b"], x2, EPS, residual=x2)
+
+
+def evit_block(w, q, x, hh, ww, c, bf):
+    """EfficientViTBlock ``q`` in place on x."""
+    from . import ops
+    npx, heads = hh * ww, c // HEAD
+    x2 = x.view(npx, c)
+    s, g, t = bf["s"], bf["g"], bf["t1"][:npx * c].view(npx, c)
+    qkv = s[:npx * 3 * c].view(npx, 3 * c)
+    agg = s[npx * 3 * c:npx * 6 * c].view(npx, 3 * c)
+    o = g[:npx * 2 * c].view(npx, 2 * c)
+    ops.gemm(x2, w[q + "qkv.w"], qkv, M=npx, N=3 * c, K=c)                                  # to_q | to_k | to_v
+    ops.dcae_msla_aggregate(qkv, w[q + "ms_dw.w"], w[q + "ms_pw.w"], agg, 1, hh, ww, 3 * c)
+    ops.linear_attn_fwd(qkv, 1, npx, heads, c, 2 * c, o[:, :c], bf["ws"])                        # base heads
+    ops.linear_attn_fwd(agg, 1, npx, heads, c, 2 * c, o[:, c:], bf["ws"])                        # aggregated heads
+    ops.gemm(o, w[q + "to_out.w"], t, M=npx, N=c, K=2 * c)
+    ops.dcae_rmsnorm_bias(t, w[q + "attn_norm.w"], w[q + "attn_norm.b"], x2, EPS, residual=x2)
+    sil = s[:npx * 8 * c].view(npx, 8 * c)
+    ops.gemm(x2, w[q + "inv.w"], sil, M=npx, N=8 * c, K=c, bias=w[q + "inv.b"], activation="silu")
+    glu = g[:npx * 4 * c].view(npx, 4 * c)
+    ops.dwconv_glu_fwd(sil, 1, hh, ww, 4 * c, w[q + "dw.w"], w[q + "dw.b"], glu)
+    ops.gemm(glu, w[q + "pt.w"], t, M=npx, N=c, K=4 * c)
+    ops.dcae_rmsnorm_bias(t, w[q + "glu_norm.w"], w[q + "glu_norm.b"], x2, EPS, residual=x2)
 
 
 class AutoencoderDCDecoderHIP:
@@ -264,50 +317,17 @@ class AutoencoderDCDecoderHIP:
     def _buffers(self, h, w):
         if self._bufs is not None and self._bufs[0] == (h, w):
             return self._bufs[1]
-        from . import ops
         self._bufs = None
-        cfg = self.cfg
-        sizes = self._stage_sizes(h, w)
-        act = max(hh * ww * c for (hh, ww), c in zip(sizes, cfg.block_out_channels))
-        evit = [(hh * ww, c) for (hh, ww), c, t in zip(sizes, cfg.block_out_channels, cfg.block_types) if t == EVIT]
-        big = max([npx * 8 * c for npx, c in evit], default=0)
-        mid = max([npx * 4 * c for npx, c in evit], default=0)
-        ws = max([ops.linear_attn_workspace_bytes(1, npx, c // HEAD) for npx, c in evit], default=0)
-        e = lambda k: torch.empty(max(k, 1), dtype=BF16, device=self.device)  # noqa: E731
-        bufs = {"xa": e(act), "xb": e(act), "t1": e(act), "t2": e(act), "s": e(big), "g": e(mid),
-                "ws": torch.empty(max(ws, 16), dtype=torch.uint8, device=self.device)}
+        bufs = alloc_buffers(self._stage_sizes(h, w), self.cfg.block_out_channels, self.cfg.block_types, self.device)
         self._bufs = ((h, w), bufs)
         return bufs
 
     # ------------------------------------------------------------------------------------------------ blocks
     def _res_block(self, q, x, hh, ww, c, bf):
-        from . import ops
-        t1, t2 = bf["t1"][:hh * ww * c], bf["t2"][:hh * ww * c]
-        ops.dcae_conv3x3(x, self.w[q + "conv1.w"], t1, 1, hh, ww, c, c, bias=self.w[q + "conv1.b"], silu=True)
-        ops.dcae_conv3x3(t1, self.w[q + "conv2.w"], t2, 1, hh, ww, c, c)
-        x2 = x.view(hh * ww, c)
-        ops.dcae_rmsnorm_bias(t2.view(hh * ww, c), self.w[q + "norm.w"], self.w[q + "norm.b"], x2, EPS, residual=x2)
+        res_block(self.w, q, x, hh, ww, c, bf)
 
     def _evit_block(self, q, x, hh, ww, c, bf):
-        from . import ops
-        npx, heads = hh * ww, c // HEAD
-        x2 = x.view(npx, c)
-        s, g, t = bf["s"], bf["g"], bf["t1"][:npx * c].view(npx, c)
-        qkv = s[:npx * 3 * c].view(npx, 3 * c)
-        agg = s[npx * 3 * c:npx * 6 * c].view(npx, 3 * c)
-        o = g[:npx * 2 * c].view(npx, 2 * c)
-        ops.gemm(x2, self.w[q + "qkv.w"], qkv, M=npx, N=3 * c, K=c)                                  # to_q | to_k | to_v
-        ops.dcae_msla_aggregate(qkv, self.w[q + "ms_dw.w"], self.w[q + "ms_pw.w"], agg, 1, hh, ww, 3 * c)
-        ops.linear_attn_fwd(qkv, 1, npx, heads, c, 2 * c, o[:, :c], bf["ws"])                        # base heads
-        ops.linear_attn_fwd(agg, 1, npx, heads, c, 2 * c, o[:, c:], bf["ws"])                        # aggregated heads
-        ops.gemm(o, self.w[q + "to_out.w"], t, M=npx, N=c, K=2 * c)
-        ops.dcae_rmsnorm_bias(t, self.w[q + "attn_norm.w"], self.w[q + "attn_norm.b"], x2, EPS, residual=x2)
-        sil = s[:npx * 8 * c].view(npx, 8 * c)
-        ops.gemm(x2, self.w[q + "inv.w"], sil, M=npx, N=8 * c, K=c, bias=self.w[q + "inv.b"], activation="silu")
-        glu = g[:npx * 4 * c].view(npx, 4 * c)
-        ops.dwconv_glu_fwd(sil, 1, hh, ww, 4 * c, self.w[q + "dw.w"], self.w[q + "dw.b"], glu)
-        ops.gemm(glu, self.w[q + "pt.w"], t, M=npx, N=c, K=4 * c)
-        ops.dcae_rmsnorm_bias(t, self.w[q + "glu_norm.w"], self.w[q + "glu_norm.b"], x2, EPS, residual=x2)
+        evit_block(self.w, q, x, hh, ww, c, bf)
 
     def _decode_one(self, z, out, h, w):
         from . import ops

@@ -838,6 +838,47 @@ def dcae_image_to_uint8(x, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------- DC-AE encoder (yat_amd/dcae_encoder.py)
+def dcae_conv3x3_down(x, w, y, B, H, W, Cin, Cout, bias=None, shortcut=True):
+    """DCDownBlock2d ("Conv" form): 3x3 conv, stride 2, pad 1 + the pixel-unshuffle group-mean shortcut, NHWC
+    (include/yat_hip.h yat_dcae_conv3x3_down); x [B, H, W, Cin] -> y [B, H/2, W/2, Cout]; w is [Cout, 3, 3, Cin]."""
+    _chk_bf16(x, w, y, bias)
+    rc = _lib().yat_dcae_conv3x3_down(B, H, W, Cin, Cout, _p(x), _p(w), _p(bias), int(shortcut), _p(y), _stream())
+    _l.check(rc, "yat_dcae_conv3x3_down")
+    return y
+
+
+def dcae_conv3x3_mean(x, w, y, B, H, W, Cin, Cout, bias=None, shortcut=True):
+    """Encoder.conv_out: 3x3 conv, pad 1 + the channel-group-mean shortcut (yat_dcae_conv3x3_mean)."""
+    _chk_bf16(x, w, y, bias)
+    rc = _lib().yat_dcae_conv3x3_mean(B, H, W, Cin, Cout, _p(x), _p(w), _p(bias), int(shortcut), _p(y), _stream())
+    _l.check(rc, "yat_dcae_conv3x3_mean")
+    return y
+
+
+_U8_TABLES = {}
+
+
+def dcae_uint8_table(device):
+    """The 256 values of ToTensor -> Normalize(0.5, 0.5) -> bf16, computed by torch itself, on ``device``."""
+    device = torch.device(device)
+    if device not in _U8_TABLES:
+        u = torch.arange(256, dtype=torch.uint8)
+        _U8_TABLES[device] = ((u.to(torch.float32).div(255) - 0.5) / 0.5).to(torch.bfloat16).to(device)
+    return _U8_TABLES[device]
+
+
+def dcae_image_from_uint8(x, out=None):
+    """[..., 3] uint8 (HWC) -> [..., 8] bf16 in [-1, 1], channels 3..7 zero (yat_dcae_image_from_uint8)."""
+    if x.dtype != torch.uint8 or x.shape[-1] != 3 or not x.is_contiguous():
+        raise ValueError("dcae_image_from_uint8 wants a contiguous [..., 3] uint8 tensor")
+    out = out if out is not None else torch.empty(*x.shape[:-1], 8, dtype=torch.bfloat16, device=x.device)
+    _chk_bf16(out)
+    rc = _lib().yat_dcae_image_from_uint8(x.numel() // 3, _p(x), _p(dcae_uint8_table(x.device)), _p(out), _stream())
+    _l.check(rc, "yat_dcae_image_from_uint8")
+    return out
+
+
 # --------------------------------------------------------------------------------- AutoencoderKL decoder (yat_amd/autoencoder_kl.py)
 def vae_groupnorm_workspace_bytes(B, HW, C, G):
     return int(_lib().yat_vae_groupnorm_workspace_bytes(B, HW, C, G))
