@@ -17,28 +17,14 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from yat_amd import dcae, ops  # noqa: E402
+from yat_amd import dcae  # noqa: E402
+from vae_bench_common import PEAK, conv_rows, instrumented, random_weights, timed  # noqa: E402
 
-PEAK = 2.5e15
 SANA_F32C32 = {"latent_channels": 32, "attention_head_dim": 32, "in_channels": 3,
                "decoder_block_out_channels": [128, 256, 512, 512, 1024, 1024],
                "decoder_block_types": ["ResBlock"] * 3 + ["EfficientViTBlock"] * 3, "decoder_layers_per_block": [3] * 6,
                "decoder_qkv_multiscales": [[], [], [], [5], [5], [5]], "decoder_norm_types": "rms_norm",
                "decoder_act_fns": "silu", "upsample_block_type": "interpolate", "scaling_factor": 0.41407}
-
-
-def random_weights(cfg, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for k, shape in dcae.expected_keys(cfg).items():
-        if len(shape) == 1:
-            sd[k] = (torch.ones(shape) if "norm" in k else 0.05 * torch.randn(shape, generator=g))
-        else:
-            fan = 1
-            for s in shape[1:]:
-                fan *= s
-            sd[k] = torch.randn(shape, generator=g) / fan ** 0.5
-    return sd
 
 
 def model_flops(cfg, h, w):
@@ -62,49 +48,18 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
     cfg = dcae.parse_config(SANA_F32C32)
-    dec = dcae.AutoencoderDCDecoderHIP(cfg, dcae.pack_weights(cfg, random_weights(cfg)), device="cuda")
+    dec = dcae.AutoencoderDCDecoderHIP(cfg, dcae.pack_weights(cfg, random_weights(dcae.expected_keys(cfg))), device="cuda")
     lat = torch.randn(1, 32, a.latent, a.latent, generator=torch.Generator().manual_seed(1)).to(torch.bfloat16).cuda()
     for _ in range(a.warmup):
-        img = dec.decode(lat)
+        dec.decode(lat)
     torch.cuda.synchronize()
-    times = []
-    for _ in range(a.repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        img = dec.decode(lat)
-        e1.record()
-        torch.cuda.synchronize()
-        times.append(e0.elapsed_time(e1))
-    ms = sorted(times)[len(times) // 2]
+    ms, times, img = timed(lambda: dec.decode(lat), a.repeats)
     flops = model_flops(cfg, a.latent, a.latent)
 
     # instrumented pass: an event pair around every 3x3 conv
-    rec = []
-    orig = ops.dcae_conv3x3
-
-    def timed(x, w, y, B, H, W, Cin, Cout, **kw):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = orig(x, w, y, B, H, W, Cin, Cout, **kw)
-        e1.record()
-        rec.append(((Cin, Cout, H, W, int(bool(kw.get("upsample")))), 2.0 * 9 * Cin * Cout * B * H * W, e0, e1))
-        return out
-    ops.dcae_conv3x3 = timed
-    try:
-        dec.decode(lat)
-        torch.cuda.synchronize()
-    finally:
-        ops.dcae_conv3x3 = orig
-    shapes = {}
-    for key, f, e0, e1 in rec:
-        s = shapes.setdefault(key, [0, 0.0, 0.0])
-        s[0] += 1
-        s[1] += e0.elapsed_time(e1)
-        s[2] += f
-    conv_ms = sum(v[1] for v in shapes.values())
-    per_shape = [{"cin": k[0], "cout": k[1], "h": k[2], "w": k[3], "upsample": k[4], "calls": v[0], "ms": round(v[1], 3),
-                  "tflops": round(v[2] / v[1] / 1e9, 1), "frac_peak": round(v[2] / v[1] / 1e-3 / PEAK, 3)}
-                 for k, v in sorted(shapes.items(), key=lambda kv: -kv[1][1])]
+    rec = instrumented({"dcae_conv3x3": lambda x, w, y, B, H, W, Cin, Cout, **kw: (
+        (Cin, Cout, H, W, int(bool(kw.get("upsample")))), 2.0 * 9 * Cin * Cout * B * H * W)}, lambda: dec.decode(lat))
+    conv_ms, per_shape = conv_rows(rec["dcae_conv3x3"], ("cin", "cout", "h", "w", "upsample"))
     print(json.dumps({"metric": "dcae_decode_ms", "image_px": 32 * a.latent, "ms_per_image": round(ms, 3),
                       "all_ms": [round(t, 3) for t in times], "model_tflop": round(flops / 1e12, 3),
                       "tflops": round(flops / ms / 1e9, 1), "frac_peak": round(flops / (ms * 1e-3) / PEAK, 3),

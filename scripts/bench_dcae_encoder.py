@@ -19,28 +19,14 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from yat_amd import dcae, dcae_encoder, ops  # noqa: E402
+from vae_bench_common import PEAK, conv_rows, instrumented, random_weights, timed  # noqa: E402
 
-PEAK = 2.5e15
 BF = torch.bfloat16
 SANA_F32C32 = {"latent_channels": 32, "attention_head_dim": 32, "in_channels": 3,
                "encoder_block_out_channels": [128, 256, 512, 512, 1024, 1024],
                "encoder_block_types": ["ResBlock"] * 3 + ["EfficientViTBlock"] * 3,
                "encoder_layers_per_block": [2, 2, 2, 3, 3, 3], "encoder_qkv_multiscales": [[], [], [], [5], [5], [5]],
                "downsample_block_type": "Conv", "scaling_factor": 0.41407}
-
-
-def random_weights(cfg, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for k, shape in dcae_encoder.expected_keys(cfg).items():
-        if len(shape) == 1:
-            sd[k] = (torch.ones(shape) if "norm" in k else 0.05 * torch.randn(shape, generator=g))
-        else:
-            fan = 1
-            for s in shape[1:]:
-                fan *= s
-            sd[k] = torch.randn(shape, generator=g) / fan ** 0.5
-    return sd
 
 
 def model_flops(cfg, H, W):
@@ -57,18 +43,6 @@ def model_flops(cfg, H, W):
     return f
 
 
-def _timed(fn, repeats):
-    times = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return sorted(times)[len(times) // 2], times
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--px", type=int, default=1024)
@@ -77,50 +51,25 @@ def main():
     ap.add_argument("--torch-ref", action="store_true", help="also time tests/dcae_encoder_ref.py in bf16 on this GPU")
     a = ap.parse_args()
     cfg = dcae_encoder.parse_encoder_config(SANA_F32C32)
-    sd = random_weights(cfg)
+    sd = random_weights(dcae_encoder.expected_keys(cfg))
     enc = dcae_encoder.AutoencoderDCEncoderHIP(cfg, dcae_encoder.pack_weights(cfg, sd), device="cuda")
     img = (torch.rand(1, 3, a.px, a.px, generator=torch.Generator().manual_seed(1)) * 2 - 1).to(BF).cuda()
     u8 = torch.randint(0, 256, (a.px, a.px, 3), generator=torch.Generator().manual_seed(2), dtype=torch.uint8).cuda()
     for _ in range(a.warmup):
-        lat = enc.encode(img)
+        enc.encode(img)
         enc.encode_uint8(u8)
     torch.cuda.synchronize()
-    ms, times = _timed(lambda: enc.encode(img), a.repeats)
-    ms_u8, _ = _timed(lambda: enc.encode_uint8(u8), a.repeats)
+    ms, times, lat = timed(lambda: enc.encode(img), a.repeats)
+    ms_u8, _, _ = timed(lambda: enc.encode_uint8(u8), a.repeats)
     flops = model_flops(cfg, a.px, a.px)
 
     # instrumented pass: an event pair around every 3x3 conv of the three kinds
-    rec = []
-
-    def wrap(name, stride):
-        orig = getattr(ops, name)
-
-        def timed(x, w, y, B, H, W, Cin, Cout, **kw):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            out = orig(x, w, y, B, H, W, Cin, Cout, **kw)
-            e1.record()
-            rec.append(((name, Cin, Cout, H, W), 2.0 * 9 * Cin * Cout * B * (H // stride) * (W // stride), e0, e1))
-            return out
-        setattr(ops, name, timed)
-        return orig
-    saved = {n: wrap(n, s) for n, s in (("dcae_conv3x3", 1), ("dcae_conv3x3_down", 2), ("dcae_conv3x3_mean", 1))}
-    try:
-        enc.encode(img)
-        torch.cuda.synchronize()
-    finally:
-        for n, o in saved.items():
-            setattr(ops, n, o)
-    shapes = {}
-    for key, f, e0, e1 in rec:
-        s = shapes.setdefault(key, [0, 0.0, 0.0])
-        s[0] += 1
-        s[1] += e0.elapsed_time(e1)
-        s[2] += f
-    conv_ms = sum(v[1] for v in shapes.values())
-    per_shape = [{"kernel": k[0], "cin": k[1], "cout": k[2], "h_in": k[3], "w_in": k[4], "calls": v[0], "ms": round(v[1], 3),
-                  "tflops": round(v[2] / v[1] / 1e9, 1), "frac_peak": round(v[2] / v[1] / 1e-3 / PEAK, 3)}
-                 for k, v in sorted(shapes.items(), key=lambda kv: -kv[1][1])]
+    def meter(name, stride):
+        return lambda x, w, y, B, H, W, Cin, Cout, **kw: (
+            (name, Cin, Cout, H, W), 2.0 * 9 * Cin * Cout * B * (H // stride) * (W // stride))
+    rec = instrumented({n: meter(n, s) for n, s in (("dcae_conv3x3", 1), ("dcae_conv3x3_down", 2), ("dcae_conv3x3_mean", 1))},
+                       lambda: enc.encode(img))
+    conv_ms, per_shape = conv_rows(sum(rec.values(), []), ("kernel", "cin", "cout", "h_in", "w_in"))
 
     # every down-block shape against the stride-1 conv at the same (M, N, K): same output grid, same Cin and Cout
     ch = cfg.block_out_channels
@@ -138,7 +87,7 @@ def main():
                           ("stride1", lambda: ops.dcae_conv3x3(x, w, y, 1, H // 2, W // 2, cin, cout, bias=b))):
             fn()
             torch.cuda.synchronize()
-            t, _ = _timed(fn, max(a.repeats, 5))
+            t, _, _ = timed(fn, max(a.repeats, 5))
             row[label + "_ms"] = round(t, 4)
             row[label + "_frac_peak"] = round(f / (t * 1e-3) / PEAK, 3)
         pairs.append(row)
@@ -156,7 +105,7 @@ def main():
         with torch.no_grad():
             dcae_encoder_ref.encode(ref_cfg, sdb, img, BF)
             torch.cuda.synchronize()
-            t, _ = _timed(lambda: dcae_encoder_ref.encode(ref_cfg, sdb, img, BF), a.repeats)
+            t, _, _ = timed(lambda: dcae_encoder_ref.encode(ref_cfg, sdb, img, BF), a.repeats)
         out["torch_bf16_restatement_ms"] = round(t, 3)
     print(json.dumps(out))
 

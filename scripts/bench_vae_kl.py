@@ -19,27 +19,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from yat_amd import autoencoder_kl as kl, ops  # noqa: E402
+from yat_amd import autoencoder_kl as kl  # noqa: E402
+from vae_bench_common import PEAK, conv_rows, instrumented, random_weights, timed  # noqa: E402
 
-PEAK = 2.5e15
 WIDTHS = {"block_out_channels": [128, 256, 512, 512], "layers_per_block": 2, "norm_num_groups": 32, "act_fn": "silu",
           "up_block_types": ["UpDecoderBlock2D"] * 4, "mid_block_add_attention": True, "out_channels": 3}
 VAES = {"sdxl": dict(WIDTHS, latent_channels=4, use_post_quant_conv=True, scaling_factor=0.13025),
         "sd35": dict(WIDTHS, latent_channels=16, use_post_quant_conv=False, scaling_factor=1.5305, shift_factor=0.0609)}
-
-
-def random_weights(cfg, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for k, shape in kl.expected_keys(cfg).items():
-        if len(shape) == 1:
-            sd[k] = torch.ones(shape) if "norm" in k else 0.05 * torch.randn(shape, generator=g)
-        else:
-            fan = 1
-            for s in shape[1:]:
-                fan *= s
-            sd[k] = torch.randn(shape, generator=g) / fan ** 0.5
-    return sd
 
 
 def model_flops(cfg, h, w):
@@ -65,64 +51,30 @@ def model_flops(cfg, h, w):
 
 def _instrument(dec, lat):
     """One decode with an event pair around every 3x3 conv, GroupNorm and attention launch."""
-    rec = {"conv": [], "gn": [], "attn": []}
-    orig = ops.dcae_conv3x3, ops.vae_groupnorm, ops.vae_attn_fwd
-
-    def timed(kind, fn, key, flops_or_bytes):
-        def call(*a, **kw):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            out = fn(*a, **kw)
-            e1.record()
-            rec[kind].append((key(*a, **kw), flops_or_bytes(*a, **kw), e0, e1))
-            return out
-        return call
-
-    ops.dcae_conv3x3 = timed("conv", orig[0], lambda x, w, y, B, H, W, Cin, Cout, **kw: (Cin, Cout, H, W, int(bool(kw.get("upsample")))),
-                             lambda x, w, y, B, H, W, Cin, Cout, **kw: 2.0 * 9 * Cin * Cout * B * H * W)
-    ops.vae_groupnorm = timed("gn", orig[1], lambda *a, **kw: None, lambda x, w, b, y, B, HW, C, *r, **kw: 3.0 * 2 * B * HW * C)
-    ops.vae_attn_fwd = timed("attn", orig[2], lambda *a, **kw: None, lambda q, k, v, o, B, N, dh, *r, **kw: 4.0 * B * N * N * dh)
-    try:
-        dec.decode(lat)
-        torch.cuda.synchronize()
-    finally:
-        ops.dcae_conv3x3, ops.vae_groupnorm, ops.vae_attn_fwd = orig
-    shapes = {}
-    for key, f, e0, e1 in rec["conv"]:
-        s = shapes.setdefault(key, [0, 0.0, 0.0])
-        s[0] += 1
-        s[1] += e0.elapsed_time(e1)
-        s[2] += f
-    per_shape = [{"cin": k[0], "cout": k[1], "h": k[2], "w": k[3], "upsample": k[4], "calls": v[0], "ms": round(v[1], 3),
-                  "tflops": round(v[2] / v[1] / 1e9, 1), "frac_peak": round(v[2] / v[1] / 1e-3 / PEAK, 3)}
-                 for k, v in sorted(shapes.items(), key=lambda kv: -kv[1][1])]
-    gn_ms = sum(e0.elapsed_time(e1) for _, _, e0, e1 in rec["gn"])
-    gn_bytes = sum(b for _, b, _, _ in rec["gn"])
-    at_ms = sum(e0.elapsed_time(e1) for _, _, e0, e1 in rec["attn"])
-    at_f = sum(f for _, f, _, _ in rec["attn"])
-    return {"conv3x3_ms_instrumented": round(sum(v[1] for v in shapes.values()), 3), "conv3x3": per_shape,
-            "groupnorm": {"calls": len(rec["gn"]), "ms": round(gn_ms, 3), "gbytes": round(gn_bytes / 1e9, 2),
+    rec = instrumented({
+        "dcae_conv3x3": lambda x, w, y, B, H, W, Cin, Cout, **kw: (
+            (Cin, Cout, H, W, int(bool(kw.get("upsample")))), 2.0 * 9 * Cin * Cout * B * H * W),
+        "vae_groupnorm": lambda x, w, b, y, B, HW, C, *r, **kw: (None, 3.0 * 2 * B * HW * C),
+        "vae_attn_fwd": lambda q, k, v, o, B, N, dh, *r, **kw: (None, 4.0 * B * N * N * dh)}, lambda: dec.decode(lat))
+    conv_ms, per_shape = conv_rows(rec["dcae_conv3x3"], ("cin", "cout", "h", "w", "upsample"))
+    gn, attn = rec["vae_groupnorm"], rec["vae_attn_fwd"]
+    gn_ms, gn_bytes = sum(ms for _, _, ms in gn), sum(b for _, b, _ in gn)
+    at_ms, at_f = sum(ms for _, _, ms in attn), sum(f for _, f, _ in attn)
+    return {"conv3x3_ms_instrumented": round(conv_ms, 3), "conv3x3": per_shape,
+            "groupnorm": {"calls": len(gn), "ms": round(gn_ms, 3), "gbytes": round(gn_bytes / 1e9, 2),
                           "gb_per_s": round(gn_bytes / gn_ms / 1e6, 1)},
-            "attention": {"calls": len(rec["attn"]), "ms": round(at_ms, 3), "tflop": round(at_f / 1e12, 3),
+            "attention": {"calls": len(attn), "ms": round(at_ms, 3), "tflop": round(at_f / 1e12, 3),
                           "tflops": round(at_f / at_ms / 1e9, 1) if at_ms else 0.0}}
 
 
 def bench(raw, latent, warmup, repeats):
     cfg = kl.parse_config(raw)
-    dec = kl.AutoencoderKLDecoderHIP(cfg, kl.pack_weights(cfg, random_weights(cfg)), device="cuda")
+    dec = kl.AutoencoderKLDecoderHIP(cfg, kl.pack_weights(cfg, random_weights(kl.expected_keys(cfg))), device="cuda")
     lat = torch.randn(1, cfg.latent_channels, latent, latent, generator=torch.Generator().manual_seed(1)).to(torch.bfloat16).cuda()
     for _ in range(warmup):
-        img = dec.decode(lat)
+        dec.decode(lat)
     torch.cuda.synchronize()
-    times = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        img = dec.decode(lat)
-        e1.record()
-        torch.cuda.synchronize()
-        times.append(e0.elapsed_time(e1))
-    ms = sorted(times)[len(times) // 2]
+    ms, times, img = timed(lambda: dec.decode(lat), repeats)
     flops = model_flops(cfg, latent, latent)
     out = {"image_px": 8 * latent, "ms_per_image": round(ms, 3), "all_ms": [round(t, 3) for t in times],
            "model_tflop": round(flops / 1e12, 3), "tflops": round(flops / ms / 1e9, 1),

@@ -11,6 +11,8 @@ shift_factor, use_post_quant_conv, mid_block_add_attention (UpDecoderBlock2D / s
 import torch
 import torch.nn.functional as F
 
+from tests.dcae_ref import postprocess, weight_drawers  # noqa: F401 (postprocess: the tests reach it through this module)
+
 EPS = 1e-6
 
 
@@ -74,25 +76,11 @@ def decode(cfg, sd, latent, dtype):
     return conv(x, sd["decoder.conv_out.weight"], sd["decoder.conv_out.bias"])
 
 
-def postprocess(x):
-    """VaeImageProcessor.postprocess (denormalize in the tensor's dtype) + numpy_to_pil's uint8: [B, 3, H, W] -> uint8."""
-    p = (x / 2 + 0.5).clamp(0, 1)
-    return (p.cpu().float() * 255).numpy().round().astype("uint8")
-
-
 def random_state(cfg, seed=0, out_channels=3):
     """Random decoder weights in the diffusers layout, bf16-representable (fp32 tensors), scaled so that activations stay
     O(1) through the stack (GroupNorm re-normalises every block input)."""
-    gen = torch.Generator().manual_seed(seed)
     ch, n, lat = list(cfg["block_out_channels"]), len(cfg["block_out_channels"]), cfg["latent_channels"]
-    sd = {}
-
-    def w(k, *shape, scale=1.0):
-        fan = shape[1] * (shape[2] * shape[3] if len(shape) == 4 else 1)
-        sd[k] = (torch.randn(*shape, generator=gen) * (scale / fan ** 0.5)).to(torch.bfloat16).float()
-
-    def vec(k, c, mean=0.0, std=0.1):
-        sd[k] = (mean + std * torch.randn(c, generator=gen)).to(torch.bfloat16).float()
+    sd, w, vec = weight_drawers(seed)
 
     def res(p, cin, cout):
         vec(p + "norm1.weight", cin, 1.0, 0.2)

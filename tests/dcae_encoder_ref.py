@@ -12,7 +12,7 @@ values as lists; the "Conv" down block, qkv_multiscales (5,), head dim 32 and rm
 import torch
 import torch.nn.functional as F
 
-from tests.dcae_ref import conv, evit_block, res_block
+from tests.dcae_ref import conv, evit_block, random_block, res_block, weight_drawers
 
 
 def down_block(x, sd, p, c_out):
@@ -44,46 +44,14 @@ def encode(cfg, sd, images, dtype):
 def random_encoder_state(cfg, seed=0, in_channels=3):
     """Random encoder weights in the diffusers layout, bf16-representable (fp32 tensors), scaled so that activations stay
     O(1) through the stack."""
-    g = torch.Generator().manual_seed(seed)
     ch, n, lat = list(cfg["block_out_channels"]), len(cfg["block_out_channels"]), cfg["latent_channels"]
-    sd = {}
-
-    def w(k, *shape, scale=1.0):
-        fan = shape[1] * (shape[2] * shape[3] if len(shape) == 4 else 1)
-        sd[k] = (torch.randn(*shape, generator=g) * (scale / fan ** 0.5)).to(torch.bfloat16).float()
-
-    def vec(k, c, mean=0.0, std=0.1):
-        sd[k] = (mean + std * torch.randn(c, generator=g)).to(torch.bfloat16).float()
-
+    sd, w, vec = weight_drawers(seed)
     w("encoder.conv_in.weight", ch[0], in_channels, 3, 3, scale=2.0)
     vec("encoder.conv_in.bias", ch[0])
     for i in range(n):
         c, nl = ch[i], cfg["layers_per_block"][i]
         for j in range(nl):
-            p = f"encoder.down_blocks.{i}.{j}."
-            if cfg["block_types"][i] == "ResBlock":
-                w(p + "conv1.weight", c, c, 3, 3)
-                vec(p + "conv1.bias", c)
-                w(p + "conv2.weight", c, c, 3, 3)
-                vec(p + "norm.weight", c, 1.0, 0.2)
-                vec(p + "norm.bias", c)
-            else:
-                a = p + "attn."
-                for t in ("to_q", "to_k", "to_v"):
-                    w(a + t + ".weight", c, c)
-                w(a + "to_qkv_multiscale.0.proj_in.weight", 3 * c, 1, 5, 5)
-                w(a + "to_qkv_multiscale.0.proj_out.weight", 3 * c, 32, 1, 1)
-                w(a + "to_out.weight", c, 2 * c)
-                vec(a + "norm_out.weight", c, 1.0, 0.2)
-                vec(a + "norm_out.bias", c)
-                gg = p + "conv_out."
-                w(gg + "conv_inverted.weight", 8 * c, c, 1, 1)
-                vec(gg + "conv_inverted.bias", 8 * c)
-                w(gg + "conv_depth.weight", 8 * c, 1, 3, 3)
-                vec(gg + "conv_depth.bias", 8 * c)
-                w(gg + "conv_point.weight", c, 4 * c, 1, 1)
-                vec(gg + "norm.weight", c, 1.0, 0.2)
-                vec(gg + "norm.bias", c)
+            random_block(w, vec, f"encoder.down_blocks.{i}.{j}.", cfg["block_types"][i], c)
         if i < n - 1:
             # the conv output adds to a shortcut of O(1 / sqrt(g)) magnitude; 0.7 keeps the sum O(1) stage after stage
             w(f"encoder.down_blocks.{i}.{nl}.conv.weight", ch[i + 1], c, 3, 3, scale=0.7)

@@ -107,20 +107,54 @@ def postprocess(x):
     return (p.cpu().float() * 255).numpy().round().astype("uint8")
 
 
-def random_state(cfg, seed=0, out_channels=3):
-    """Random decoder weights in the diffusers layout, bf16-representable (fp32 tensors), scaled so that activations stay
-    O(1) through the stack."""
+def weight_drawers(seed):
+    """(sd, w, vec): ``w(key, *shape, scale=1.0)`` draws a weight of std scale / sqrt(fan-in) into ``sd``, ``vec(key, c, mean,
+    std)`` a vector, both bf16-representable fp32 tensors from one generator seeded ``seed``."""
     g = torch.Generator().manual_seed(seed)
-    ch, n, lat = list(cfg["block_out_channels"]), len(cfg["block_out_channels"]), cfg["latent_channels"]
     sd = {}
 
-    def w(k, *shape, fan_in=None, scale=1.0):
-        fan = fan_in if fan_in is not None else (shape[1] * (shape[2] * shape[3] if len(shape) == 4 else 1))
+    def w(k, *shape, scale=1.0):
+        fan = shape[1] * (shape[2] * shape[3] if len(shape) == 4 else 1)
         sd[k] = (torch.randn(*shape, generator=g) * (scale / fan ** 0.5)).to(torch.bfloat16).float()
 
     def vec(k, c, mean=0.0, std=0.1):
         sd[k] = (mean + std * torch.randn(c, generator=g)).to(torch.bfloat16).float()
 
+    return sd, w, vec
+
+
+def random_block(w, vec, p, block_type, c):
+    """Draws the weights of one ResBlock / EfficientViTBlock of width ``c`` under the prefix ``p``."""
+    if block_type == "ResBlock":
+        w(p + "conv1.weight", c, c, 3, 3)
+        vec(p + "conv1.bias", c)
+        w(p + "conv2.weight", c, c, 3, 3)
+        vec(p + "norm.weight", c, 1.0, 0.2)
+        vec(p + "norm.bias", c)
+        return
+    a = p + "attn."
+    for t in ("to_q", "to_k", "to_v"):
+        w(a + t + ".weight", c, c)
+    w(a + "to_qkv_multiscale.0.proj_in.weight", 3 * c, 1, 5, 5)
+    w(a + "to_qkv_multiscale.0.proj_out.weight", 3 * c, 32, 1, 1)
+    w(a + "to_out.weight", c, 2 * c)
+    vec(a + "norm_out.weight", c, 1.0, 0.2)
+    vec(a + "norm_out.bias", c)
+    gg = p + "conv_out."
+    w(gg + "conv_inverted.weight", 8 * c, c, 1, 1)
+    vec(gg + "conv_inverted.bias", 8 * c)
+    w(gg + "conv_depth.weight", 8 * c, 1, 3, 3)
+    vec(gg + "conv_depth.bias", 8 * c)
+    w(gg + "conv_point.weight", c, 4 * c, 1, 1)
+    vec(gg + "norm.weight", c, 1.0, 0.2)
+    vec(gg + "norm.bias", c)
+
+
+def random_state(cfg, seed=0, out_channels=3):
+    """Random decoder weights in the diffusers layout, bf16-representable (fp32 tensors), scaled so that activations stay
+    O(1) through the stack."""
+    ch, n, lat = list(cfg["block_out_channels"]), len(cfg["block_out_channels"]), cfg["latent_channels"]
+    sd, w, vec = weight_drawers(seed)
     w("decoder.conv_in.weight", ch[-1], lat, 3, 3)
     vec("decoder.conv_in.bias", ch[-1])
     for i in range(n):
@@ -130,30 +164,7 @@ def random_state(cfg, seed=0, out_channels=3):
             vec(f"decoder.up_blocks.{i}.0.conv.bias", c)
             j = 1
         for jj in range(j, j + cfg["layers_per_block"][i]):
-            p = f"decoder.up_blocks.{i}.{jj}."
-            if cfg["block_types"][i] == "ResBlock":
-                w(p + "conv1.weight", c, c, 3, 3)
-                vec(p + "conv1.bias", c)
-                w(p + "conv2.weight", c, c, 3, 3)
-                vec(p + "norm.weight", c, 1.0, 0.2)
-                vec(p + "norm.bias", c)
-            else:
-                a = p + "attn."
-                for t in ("to_q", "to_k", "to_v"):
-                    w(a + t + ".weight", c, c)
-                w(a + "to_qkv_multiscale.0.proj_in.weight", 3 * c, 1, 5, 5)
-                w(a + "to_qkv_multiscale.0.proj_out.weight", 3 * c, 32, 1, 1)
-                w(a + "to_out.weight", c, 2 * c)
-                vec(a + "norm_out.weight", c, 1.0, 0.2)
-                vec(a + "norm_out.bias", c)
-                gg = p + "conv_out."
-                w(gg + "conv_inverted.weight", 8 * c, c, 1, 1)
-                vec(gg + "conv_inverted.bias", 8 * c)
-                w(gg + "conv_depth.weight", 8 * c, 1, 3, 3)
-                vec(gg + "conv_depth.bias", 8 * c)
-                w(gg + "conv_point.weight", c, 4 * c, 1, 1)
-                vec(gg + "norm.weight", c, 1.0, 0.2)
-                vec(gg + "norm.bias", c)
+            random_block(w, vec, f"decoder.up_blocks.{i}.{jj}.", cfg["block_types"][i], c)
     vec("decoder.norm_out.weight", ch[0], 1.0, 0.2)
     vec("decoder.norm_out.bias", ch[0])
     w("decoder.conv_out.weight", out_channels, ch[0], 3, 3)

@@ -12,19 +12,9 @@ import torch
 import torch.nn.functional as F
 
 from tests import autoencoder_kl_ref as klref
+from tests.gpu_common import BF, DEV, ROOT, _rbf, _rel
 
 pytestmark = pytest.mark.gpu
-BF = torch.bfloat16
-DEV = "cuda"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _rbf(t):
-    return t.to(BF).float()
-
-
-def _rel(a, b):
-    return ((a.float() - b.float()).norm() / b.float().norm()).item()
 
 
 def _ulp(t):

@@ -26,9 +26,9 @@ from yat_amd.common.trainer import Model
 from yat_amd.autoencoder_kl import decode_validation, load_vae_decoder
 from yat_amd.common.aspect_ratios import table_for_resolution
 from yat_amd.pixart import PixArtConfig, PixArtTransformer2DModelHIP
-from yat_amd.dcae import find_vae_dir
 from yat_amd.recipe import PixArtRecipe
 from yat_amd.scheduler import DDPMSchedule
+from yat_amd.vae_common import find_vae_dir
 
 
 class PixartSigmaTrainer(Model):

@@ -21,10 +21,10 @@ import torch
 from yat_amd.common.training_parameters_reader import TrainingParameters
 from yat_amd.common.trainer import Model
 from yat_amd.common.aspect_ratios import table_for_resolution
-from yat_amd.dcae import find_vae_dir
 from yat_amd.recipe import SanaRecipe
 from yat_amd.sana import SanaConfig, SanaTransformer2DModelHIP
 from yat_amd.scheduler import FlowMatchSchedule
+from yat_amd.vae_common import decode_validation, find_vae_dir
 
 
 class SanaModel(Model):
@@ -101,18 +101,10 @@ class SanaModel(Model):
         return out
 
     def _decode_validation(self, latents):
-        from yat_amd.common.tb_writer import encode_png
-        from yat_amd.dcae import AutoencoderDCDecoderHIP
         if self.vae is None:
+            from yat_amd.dcae import AutoencoderDCDecoderHIP
             self.vae = AutoencoderDCDecoderHIP.from_pretrained(self.vae_dir, device=self.accelerator.device)
-        prompts = list(self.params.validation_prompts or [])
-        for idx, lat in enumerate(latents):
-            img = self.vae.to_uint8(self.vae.decode(lat))[0].cpu()
-            with open(f"models/{self.global_step}/validation_{idx}.png", "wb") as f:
-                f.write(encode_png(img))
-            if self.logger is not None:
-                tag = f"validation/{idx}/{prompts[idx]}" if idx < len(prompts) else f"validation/{idx}"
-                self.logger.add_image(tag, img, self.global_step)
+        decode_validation(self.vae, latents, self.params.validation_prompts, self.global_step, self.logger)
 
     def optimize(self, ratio, latents, embeddings, repa_tokens, generator: torch.Generator = None):
         """train_sana.py:163-219 on the HIP path.  With gradients enabled (the training call, common/trainer.py:337) the step

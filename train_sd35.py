@@ -28,10 +28,10 @@ from yat_amd.common.training_parameters_reader import TrainingParameters
 from yat_amd.common.trainer import Model
 from yat_amd.autoencoder_kl import decode_validation, load_vae_decoder
 from yat_amd.common.aspect_ratios import ASPECT_RATIO_1024_BIN
-from yat_amd.dcae import find_vae_dir
 from yat_amd.recipe import SD3Recipe
 from yat_amd.scheduler import FlowMatchSchedule
 from yat_amd.sd3 import SD3Config, SD3Transformer2DModelHIP
+from yat_amd.vae_common import find_vae_dir
 
 
 class SD35Trainer(Model):

@@ -27,19 +27,19 @@ padded channels stay exactly zero and contribute exactly zero.
 The SD3.5 reference divides by ``scaling_factor`` and does NOT add ``shift_factor`` back before decoding
 (train_sd35.py:155), although diffusers' own SD3 pipeline does; this decoder keeps the reference's outward contract: the
 pre-scale is ``latent / scaling_factor`` for every KL VAE, ``shift_factor`` is parsed and never applied.
+
+Directory loading, the strict key check, the buffer cache, ``decode_validation`` and the command line:
+yat_amd/vae_common.py.
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
 from dataclasses import dataclass
 
 import torch
 
-from .dcae import pack_conv3x3
+from .vae_common import (BF16, VAEHalfHIP, check_expected, decode_validation, latents_to_png_main, load_tensors,  # noqa: F401
+                         pack_conv3x3, read_config, to_uint8)
 
-BF16 = torch.bfloat16
 EPS = 1e-6
 UP = "UpDecoderBlock2D"
 ATTN_DIMS = (64, 512)            # single-head attention widths the library builds (yat_vae_attn_fwd)
@@ -189,16 +189,7 @@ def check_state(cfg: KLDecoderConfig, sd: dict) -> None:
     """Strict load: every expected key present with its shape, and no other ``decoder.`` / ``post_quant_conv.`` key (encoder
     and quant_conv keys are ignored).  ``sd`` uses the current names (``convert_deprecated``).  Raises KeyError / ValueError
     naming the key."""
-    want = expected_keys(cfg)
-    for k, shape in want.items():
-        if k not in sd:
-            raise KeyError(f"AutoencoderKL decoder weight {k!r} is missing from the checkpoint")
-        if tuple(sd[k].shape) != shape:
-            raise ValueError(f"AutoencoderKL decoder weight {k!r} has shape {tuple(sd[k].shape)}, expected {shape}")
-    extra = sorted(k for k in sd if _ours(k) and k not in want)
-    if extra:
-        raise KeyError(f"AutoencoderKL decoder weight {extra[0]!r} is not consumed by this decoder "
-                       f"({len(extra)} unconsumed key(s))")
+    check_expected(expected_keys(cfg), sd, _ours, "AutoencoderKL decoder", "this decoder")
 
 
 def pad_latent_channels(t: torch.Tensor, n: int, dim: int) -> torch.Tensor:
@@ -249,44 +240,19 @@ def pack_weights(cfg: KLDecoderConfig, sd: dict) -> dict:
     return {k: v.contiguous() for k, v in out.items()}
 
 
-def read_config(vae_dir: str) -> dict:
-    with open(os.path.join(vae_dir, "config.json")) as f:
-        return json.load(f)
-
-
 def load_vae_dir(vae_dir: str):
     """(config, ``decoder.*`` + ``post_quant_conv.*`` tensors) of a diffusers AutoencoderKL directory."""
-    from safetensors import safe_open
-    cfg = parse_config(read_config(vae_dir))
-    sd = {}
-    with safe_open(os.path.join(vae_dir, "diffusion_pytorch_model.safetensors"), framework="pt") as f:
-        for k in f.keys():
-            if _ours(k):
-                sd[k] = f.get_tensor(k)
-    return cfg, sd
+    return parse_config(read_config(vae_dir)), load_tensors(vae_dir, _ours)
 
 
-class AutoencoderKLDecoderHIP:
+class AutoencoderKLDecoderHIP(VAEHalfHIP):
     """The decoder half of AutoencoderKL in bf16 on the HIP kernels.  ``decode`` runs one image at a time on the current
     stream through activation buffers sized for the largest stage (kept between calls of the same latent size)."""
+    load_vae_dir = staticmethod(load_vae_dir)
+    pack_weights = staticmethod(pack_weights)
 
-    def __init__(self, cfg: KLDecoderConfig, packed: dict, device="cuda"):
-        self.cfg = cfg
-        self.device = torch.device(device)
-        self.w = {k: v.to(self.device, BF16).contiguous() for k, v in packed.items()}
-        self._bufs = None
-
-    @classmethod
-    def from_pretrained(cls, vae_dir: str, device="cuda"):
-        cfg, sd = load_vae_dir(vae_dir)
-        return cls(cfg, pack_weights(cfg, sd), device)
-
-    # ------------------------------------------------------------------------------------------------ buffers
-    def _buffers(self, h, w):
-        if self._bufs is not None and self._bufs[0] == (h, w):
-            return self._bufs[1]
+    def _alloc_buffers(self, h, w):
         from . import ops
-        self._bufs = None
         cfg, ch = self.cfg, self.cfg.block_out_channels
         rev = list(reversed(ch))
         # the largest activation: a block's widest input or output at its resolution, or its upsampled output
@@ -300,10 +266,8 @@ class AutoencoderKLDecoderHIP:
         ws = max(ops.vae_groupnorm_workspace_bytes(1, hh * ww, ch[0], cfg.norm_num_groups),
                  ops.vae_groupnorm_workspace_bytes(1, h * w, ch[-1], cfg.norm_num_groups))
         e = lambda k: torch.empty(max(k, 8), dtype=BF16, device=self.device)  # noqa: E731
-        bufs = {"xa": e(act), "xb": e(act), "t": e(act), "u": e(max(act, 3 * h * w * ch[-1])),
+        return {"xa": e(act), "xb": e(act), "t": e(act), "u": e(max(act, 3 * h * w * ch[-1])),
                 "z": e(h * w * cfg.latent_padded), "ws": torch.empty(max(ws, 16), dtype=torch.uint8, device=self.device)}
-        self._bufs = ((h, w), bufs)
-        return bufs
 
     # ------------------------------------------------------------------------------------------------ blocks
     def _gn(self, x, y, npx, c, key, silu, bf):
@@ -397,12 +361,6 @@ class AutoencoderKLDecoderHIP:
             self._decode_one(zb, out[b], h, w)
         return out
 
-    @staticmethod
-    def to_uint8(images: torch.Tensor) -> torch.Tensor:
-        """VaeImageProcessor.postprocess(output_type='pil') up to the PIL image: [B, 3, H, W] bf16 -> uint8 (CHW)."""
-        from . import ops
-        return ops.dcae_image_to_uint8(images.contiguous())
-
 
 def pre_scale(latents: torch.Tensor, cfg: KLDecoderConfig) -> torch.Tensor:
     """``bf16(latent / scaling_factor)``, the argument of ``vae.decode`` in both references; no ``shift_factor`` (the SD3.5
@@ -433,44 +391,8 @@ def load_vae_decoder(vae_dir: str, device="cuda"):
     return AutoencoderKLDecoderHIP.from_pretrained(vae_dir, device=device)
 
 
-def to_uint8(images: torch.Tensor) -> torch.Tensor:
-    return AutoencoderKLDecoderHIP.to_uint8(images)
-
-
-def decode_validation(vae, latents, prompts, step, logger):
-    """The last third of the PixArt-Sigma / SD3.5 ``validate()`` (train_pixart_sigma.py:137-144, train_sd35.py:150-156):
-    each latent decoded, written to models/<step>/validation_{idx}.png and logged as ``validation/{idx}/{prompt}``."""
-    from .common.tb_writer import encode_png
-    prompts = list(prompts or [])
-    for idx, lat in enumerate(latents):
-        img = vae.to_uint8(vae.decode(lat if lat.dim() == 4 else lat[None]))[0].cpu()
-        with open(f"models/{step}/validation_{idx}.png", "wb") as f:
-            f.write(encode_png(img))
-        if logger is not None:
-            tag = f"validation/{idx}/{prompts[idx]}" if idx < len(prompts) else f"validation/{idx}"
-            logger.add_image(tag, img, step)
-
-
 def main(argv=None) -> None:
-    ap = argparse.ArgumentParser(prog="python -m yat_amd.autoencoder_kl",
-                                 description="decode a validation_latents.pt (list of [1, C, h, w]) into PNG files")
-    ap.add_argument("--vae", required=True, help="diffusers AutoencoderKL directory (config.json + safetensors)")
-    ap.add_argument("--device", default="cuda")
-    ap.add_argument("latents")
-    ap.add_argument("out_dir")
-    a = ap.parse_args(argv)
-    from .common.tb_writer import encode_png
-    dec = AutoencoderKLDecoderHIP.from_pretrained(a.vae, device=a.device)
-    lats = torch.load(a.latents, map_location="cpu")
-    if isinstance(lats, torch.Tensor):
-        lats = list(lats.unsqueeze(1)) if lats.dim() == 4 else [lats]
-    os.makedirs(a.out_dir, exist_ok=True)
-    for idx, lat in enumerate(lats):
-        img = dec.to_uint8(dec.decode(lat if lat.dim() == 4 else lat[None]))[0].cpu()
-        path = os.path.join(a.out_dir, f"validation_{idx}.png")
-        with open(path, "wb") as f:
-            f.write(encode_png(img))
-        print(path)
+    latents_to_png_main("python -m yat_amd.autoencoder_kl", "AutoencoderKL", AutoencoderKLDecoderHIP, argv)
 
 
 if __name__ == "__main__":

@@ -22,17 +22,19 @@ reshape takes head g's q, k, v from 32-channel blocks 3g, 3g+1, 3g+2 of ``cat(to
 block 3g+j to position j*H + g in the fused qkv weight and in both aggregate convs (a block permutation commutes with
 the per-channel 5x5 and the per-block 1x1).  One attention call over the base qkv and one over the aggregate then write
 to_out's input columns [0, C) and [C, 2C) in diffusers' head order.
+
+Directory loading, the strict key check, the buffer cache and the command line: yat_amd/vae_common.py.  The per-stage
+config parsing and checks and the blocks below also serve the encoder (yat_amd/dcae_encoder.py).
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
 from dataclasses import dataclass
 
 import torch
 
-BF16 = torch.bfloat16
+from .vae_common import (BF16, VAEHalfHIP, check_expected, find_vae_dir, latents_to_png_main, load_tensors,  # noqa: F401
+                         pack_conv3x3, read_config, to_uint8)
+
 RES, EVIT = "ResBlock", "EfficientViTBlock"
 EPS = 1e-5
 HEAD = 32
@@ -57,7 +59,7 @@ class DCAEDecoderConfig:
         return len(self.block_out_channels)
 
 
-def _per_stage(v, n, name):
+def per_stage(v, n, name):
     if isinstance(v, (list, tuple)):
         if len(v) != n:
             raise ValueError(f"{name}: {len(v)} entries for {n} decoder stages")
@@ -65,25 +67,61 @@ def _per_stage(v, n, name):
     return (v,) * n
 
 
-def parse_config(raw: dict) -> DCAEDecoderConfig:
-    """``vae/config.json`` (AutoencoderDC) -> the decoder's configuration.  Per-stage keys may be a scalar (every stage) or
-    a list (one entry per stage); ``decoder_qkv_multiscales`` a list of kernel sizes (every stage) or a list of lists."""
-    chans = tuple(int(c) for c in raw["decoder_block_out_channels"])
+def parse_stages(raw: dict, side: str):
+    """The per-stage keys of one half (``side``: 'decoder' / 'encoder') of an AutoencoderDC ``config.json`` -> (widths, block
+    types, layers, qkv multiscales), one entry per stage.  A key may be a scalar (every stage) or a list (one entry per
+    stage); ``{side}_qkv_multiscales`` a list of kernel sizes (every stage) or a list of lists."""
+    chans = tuple(int(c) for c in raw[f"{side}_block_out_channels"])
     n = len(chans)
-    types = _per_stage(raw.get("decoder_block_types", RES), n, "decoder_block_types")
-    layers = tuple(int(v) for v in _per_stage(raw.get("decoder_layers_per_block", 2), n, "decoder_layers_per_block"))
-    ms = raw.get("decoder_qkv_multiscales", ())
+    types = per_stage(raw.get(f"{side}_block_types", RES), n, f"{side}_block_types")
+    layers = tuple(int(v) for v in per_stage(raw.get(f"{side}_layers_per_block", 2), n, f"{side}_layers_per_block"))
+    ms = raw.get(f"{side}_qkv_multiscales", ())
     if isinstance(ms, (list, tuple)) and ms and all(isinstance(m, (list, tuple)) for m in ms):
-        ms = tuple(tuple(int(k) for k in m) for m in _per_stage(list(ms), n, "decoder_qkv_multiscales"))
+        ms = tuple(tuple(int(k) for k in m) for m in per_stage(list(ms), n, f"{side}_qkv_multiscales"))
     elif isinstance(ms, (list, tuple)):
         ms = (tuple(int(k) for k in ms),) * n
     else:
         ms = ((int(ms),),) * n
+    return chans, types, layers, ms
+
+
+def validate_stages(cfg, side: str, shortcut: str, extra=None) -> None:
+    """The per-stage refusals both halves make; ``shortcut`` names the side's resampling block ('up' / 'down') and
+    ``extra(i, block_type)`` makes the side's own per-stage checks, after the block-type check."""
+    ch = cfg.block_out_channels
+    for i, (c, t, nl, ms) in enumerate(zip(ch, cfg.block_types, cfg.layers_per_block, cfg.qkv_multiscales)):
+        if t not in (RES, EVIT):
+            raise NotImplementedError(f"{side} stage {i}: block type {t!r} (built: {RES}, {EVIT})")
+        if extra is not None:
+            extra(i, t)
+        if t == EVIT and (tuple(ms) != (5,) or cfg.attention_head_dim != HEAD):
+            raise NotImplementedError(f"{side} stage {i}: qkv_multiscales {ms} / head dim {cfg.attention_head_dim} "
+                                      f"(built: (5,) / {HEAD})")
+        if nl <= 0:
+            raise NotImplementedError(f"{side} stage {i}: {nl} layers (a stage without blocks is not built)")
+        if c % 8 or (t == EVIT and c % HEAD):
+            raise ValueError(f"{side} stage {i}: {c} channels")
+        if i + 1 < len(ch) and (4 * c) % ch[i + 1]:
+            raise ValueError(f"{side} stage {i}: the {shortcut}-block shortcut needs 4*{c} % {ch[i + 1]} == 0")
+
+
+def refuse_quadratic_grids(sizes, cfg) -> None:
+    """``sizes``: the (h, w) of every stage.  diffusers' multiscale attention is linear only above head-dim pixels."""
+    for (hh, ww), t in zip(sizes, cfg.block_types):
+        if t == EVIT and hh * ww <= cfg.attention_head_dim:
+            raise ValueError(f"a {hh}x{ww} grid switches diffusers' multiscale attention to its quadratic form "
+                             "(h*w <= 32), which is not built")
+
+
+def parse_config(raw: dict) -> DCAEDecoderConfig:
+    """``vae/config.json`` (AutoencoderDC) -> the decoder's configuration (``parse_stages`` for the per-stage keys)."""
+    chans, types, layers, ms = parse_stages(raw, "decoder")
+    n = len(chans)
     cfg = DCAEDecoderConfig(
         latent_channels=int(raw.get("latent_channels", 32)), block_out_channels=chans, block_types=types,
         layers_per_block=layers, qkv_multiscales=ms,
-        norm_types=_per_stage(raw.get("decoder_norm_types", "rms_norm"), n, "decoder_norm_types"),
-        act_fns=_per_stage(raw.get("decoder_act_fns", "silu"), n, "decoder_act_fns"),
+        norm_types=per_stage(raw.get("decoder_norm_types", "rms_norm"), n, "decoder_norm_types"),
+        act_fns=per_stage(raw.get("decoder_act_fns", "silu"), n, "decoder_act_fns"),
         upsample_block_type=raw.get("upsample_block_type", "pixel_shuffle"),
         scaling_factor=float(raw.get("scaling_factor", 1.0)), attention_head_dim=int(raw.get("attention_head_dim", HEAD)),
         out_channels=int(raw.get("in_channels", 3)))
@@ -94,23 +132,13 @@ def parse_config(raw: dict) -> DCAEDecoderConfig:
 def _validate(cfg: DCAEDecoderConfig) -> None:
     if cfg.upsample_block_type != "interpolate":
         raise NotImplementedError(f"upsample_block_type {cfg.upsample_block_type!r}: only 'interpolate' is built")
-    for i, (c, t, nl, nt, act, ms) in enumerate(zip(cfg.block_out_channels, cfg.block_types, cfg.layers_per_block,
-                                                    cfg.norm_types, cfg.act_fns, cfg.qkv_multiscales)):
-        if t not in (RES, EVIT):
-            raise NotImplementedError(f"decoder stage {i}: block type {t!r} (built: {RES}, {EVIT})")
-        if nt != "rms_norm":
-            raise NotImplementedError(f"decoder stage {i}: norm type {nt!r} (built: 'rms_norm')")
-        if t == RES and act != "silu":
-            raise NotImplementedError(f"decoder stage {i}: activation {act!r} (built: 'silu')")
-        if t == EVIT and (tuple(ms) != (5,) or cfg.attention_head_dim != HEAD):
-            raise NotImplementedError(f"decoder stage {i}: qkv_multiscales {ms} / head dim {cfg.attention_head_dim} "
-                                      f"(built: (5,) / {HEAD})")
-        if nl <= 0:
-            raise NotImplementedError(f"decoder stage {i}: {nl} layers (a stage without blocks is not built)")
-        if c % 8 or (t == EVIT and c % HEAD):
-            raise ValueError(f"decoder stage {i}: {c} channels")
-        if i + 1 < cfg.num_stages and (4 * c) % cfg.block_out_channels[i + 1]:
-            raise ValueError(f"decoder stage {i}: the up-block shortcut needs 4*{c} % {cfg.block_out_channels[i + 1]} == 0")
+
+    def norm_and_act(i, t):
+        if cfg.norm_types[i] != "rms_norm":
+            raise NotImplementedError(f"decoder stage {i}: norm type {cfg.norm_types[i]!r} (built: 'rms_norm')")
+        if t == RES and cfg.act_fns[i] != "silu":
+            raise NotImplementedError(f"decoder stage {i}: activation {cfg.act_fns[i]!r} (built: 'silu')")
+    validate_stages(cfg, "decoder", "up", norm_and_act)
     if cfg.block_out_channels[-1] % cfg.latent_channels or cfg.latent_channels % 8:
         raise ValueError(f"conv_in shortcut: {cfg.block_out_channels[-1]} % {cfg.latent_channels} != 0")
     if cfg.out_channels > 4:
@@ -152,16 +180,8 @@ def expected_keys(cfg: DCAEDecoderConfig) -> dict:
 def check_state(cfg: DCAEDecoderConfig, sd: dict) -> None:
     """Strict load: every expected ``decoder.`` key present with its shape, and no other ``decoder.`` key (encoder keys are
     ignored).  Raises KeyError / ValueError naming the key."""
-    want = expected_keys(cfg)
-    for k, shape in want.items():
-        if k not in sd:
-            raise KeyError(f"DC-AE decoder weight {k!r} is missing from the checkpoint")
-        if tuple(sd[k].shape) != shape:
-            raise ValueError(f"DC-AE decoder weight {k!r} has shape {tuple(sd[k].shape)}, expected {shape}")
-    extra = sorted(k for k in sd if k.startswith("decoder.") and k not in want)
-    if extra:
-        raise KeyError(f"DC-AE decoder weight {extra[0]!r} is not consumed by the {cfg.block_types} decoder "
-                       f"({len(extra)} unconsumed key(s))")
+    check_expected(expected_keys(cfg), sd, lambda k: k.startswith("decoder."), "DC-AE decoder",
+                   f"the {cfg.block_types} decoder")
 
 
 def qkv_block_perm(heads: int) -> torch.Tensor:
@@ -174,11 +194,6 @@ def permute_blocks(t: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
     """Rows of ``t`` ([3C, ...]) regrouped in blocks of 32 by ``perm``."""
     nb = perm.numel()
     return t.reshape(nb, HEAD, *t.shape[1:])[perm].reshape(t.shape)
-
-
-def pack_conv3x3(w: torch.Tensor) -> torch.Tensor:
-    """torch [Cout, Cin, 3, 3] -> [Cout, 3, 3, Cin] (K = 9 Cin contiguous, tap-major)."""
-    return w.permute(0, 2, 3, 1).contiguous()
 
 
 def pack_block(b: dict, p: str, q: str, block_type: str, c: int) -> dict:
@@ -222,25 +237,9 @@ def pack_weights(cfg: DCAEDecoderConfig, sd: dict) -> dict:
     return out
 
 
-def find_vae_dir(pretrained_pipe_path) -> str | None:
-    """``<pipe>/vae`` when it holds a ``config.json`` (the decoder SanaModel.validate builds), else None."""
-    if not pretrained_pipe_path:
-        return None
-    d = os.path.join(pretrained_pipe_path, "vae")
-    return d if os.path.isfile(os.path.join(d, "config.json")) else None
-
-
 def load_vae_dir(vae_dir: str):
     """(config, ``decoder.*`` tensors) of a diffusers AutoencoderDC directory."""
-    from safetensors import safe_open
-    with open(os.path.join(vae_dir, "config.json")) as f:
-        cfg = parse_config(json.load(f))
-    sd = {}
-    with safe_open(os.path.join(vae_dir, "diffusion_pytorch_model.safetensors"), framework="pt") as f:
-        for k in f.keys():
-            if k.startswith("decoder."):
-                sd[k] = f.get_tensor(k)
-    return cfg, sd
+    return parse_config(read_config(vae_dir)), load_tensors(vae_dir, lambda k: k.startswith("decoder."))
 
 
 def alloc_buffers(sizes, channels, block_types, device) -> dict:
@@ -291,43 +290,21 @@ def evit_block(w, q, x, hh, ww, c, bf):
     ops.dcae_rmsnorm_bias(t, w[q + "glu_norm.w"], w[q + "glu_norm.b"], x2, EPS, residual=x2)
 
 
-class AutoencoderDCDecoderHIP:
+class AutoencoderDCDecoderHIP(VAEHalfHIP):
     """The decoder half of AutoencoderDC in bf16 on the HIP kernels.  ``decode`` runs one image at a time on the current
     stream through activation buffers sized for the largest stage (kept between calls of the same latent size).
 
     The reference decodes with ``vae.enable_tiling(2048, 2048)`` (train_sana.py:57): at 2048 px and above its output is
     stitched from tiles, so it differs from this untiled decode along the tile seams; below that both decode whole."""
+    load_vae_dir = staticmethod(load_vae_dir)
+    pack_weights = staticmethod(pack_weights)
 
-    def __init__(self, cfg: DCAEDecoderConfig, packed: dict, device="cuda"):
-        self.cfg = cfg
-        self.device = torch.device(device)
-        self.w = {k: v.to(self.device, BF16).contiguous() for k, v in packed.items()}
-        self._bufs = None
-
-    @classmethod
-    def from_pretrained(cls, vae_dir: str, device="cuda"):
-        cfg, sd = load_vae_dir(vae_dir)
-        return cls(cfg, pack_weights(cfg, sd), device)
-
-    # ------------------------------------------------------------------------------------------------ buffers
     def _stage_sizes(self, h, w):
         n = self.cfg.num_stages
         return [(h << (n - 1 - i), w << (n - 1 - i)) for i in range(n)]
 
-    def _buffers(self, h, w):
-        if self._bufs is not None and self._bufs[0] == (h, w):
-            return self._bufs[1]
-        self._bufs = None
-        bufs = alloc_buffers(self._stage_sizes(h, w), self.cfg.block_out_channels, self.cfg.block_types, self.device)
-        self._bufs = ((h, w), bufs)
-        return bufs
-
-    # ------------------------------------------------------------------------------------------------ blocks
-    def _res_block(self, q, x, hh, ww, c, bf):
-        res_block(self.w, q, x, hh, ww, c, bf)
-
-    def _evit_block(self, q, x, hh, ww, c, bf):
-        evit_block(self.w, q, x, hh, ww, c, bf)
+    def _alloc_buffers(self, h, w):
+        return alloc_buffers(self._stage_sizes(h, w), self.cfg.block_out_channels, self.cfg.block_types, self.device)
 
     def _decode_one(self, z, out, h, w):
         from . import ops
@@ -348,8 +325,8 @@ class AutoencoderDCDecoderHIP:
                 x, cur, other = y, other, cur
                 j0 = 1
             for j in range(j0, j0 + cfg.layers_per_block[i]):
-                blk = self._res_block if cfg.block_types[i] == RES else self._evit_block
-                blk(f"{i}.{j}.", x, hh, ww, c, bf)
+                blk = res_block if cfg.block_types[i] == RES else evit_block
+                blk(self.w, f"{i}.{j}.", x, hh, ww, c, bf)
         t = bf["t1"][:hh * ww * ch[0]]
         ops.dcae_rmsnorm_bias(x.view(hh * ww, ch[0]), self.w["norm_out.w"], self.w["norm_out.b"], t.view(hh * ww, ch[0]),
                               EPS, relu=True)
@@ -364,10 +341,7 @@ class AutoencoderDCDecoderHIP:
         if latents.dim() != 4 or latents.shape[1] != cfg.latent_channels:
             raise ValueError(f"latents must be [B, {cfg.latent_channels}, h, w], got {tuple(latents.shape)}")
         B, _, h, w = latents.shape
-        for (hh, ww), t in zip(self._stage_sizes(h, w), cfg.block_types):
-            if t == EVIT and hh * ww <= cfg.attention_head_dim:
-                raise ValueError(f"a {hh}x{ww} grid switches diffusers' multiscale attention to its quadratic form "
-                                 "(h*w <= 32), which is not built")
+        refuse_quadratic_grids(self._stage_sizes(h, w), cfg)
         f = 1 << (cfg.num_stages - 1)
         z = (latents.to(self.device).float() / cfg.scaling_factor).to(BF16).permute(0, 2, 3, 1).contiguous()
         out = torch.empty(B, cfg.out_channels, h * f, w * f, dtype=BF16, device=self.device)
@@ -375,37 +349,9 @@ class AutoencoderDCDecoderHIP:
             self._decode_one(z[b], out[b], h, w)
         return out
 
-    @staticmethod
-    def to_uint8(images: torch.Tensor) -> torch.Tensor:
-        """VaeImageProcessor.postprocess(output_type='pil') up to the PIL image: [B, 3, H, W] bf16 -> uint8 (CHW)."""
-        from . import ops
-        return ops.dcae_image_to_uint8(images.contiguous())
-
-
-def to_uint8(images: torch.Tensor) -> torch.Tensor:
-    return AutoencoderDCDecoderHIP.to_uint8(images)
-
 
 def main(argv=None) -> None:
-    ap = argparse.ArgumentParser(prog="python -m yat_amd.dcae",
-                                 description="decode a validation_latents.pt (list of [1, C, h, w]) into PNG files")
-    ap.add_argument("--vae", required=True, help="diffusers AutoencoderDC directory (config.json + safetensors)")
-    ap.add_argument("--device", default="cuda")
-    ap.add_argument("latents")
-    ap.add_argument("out_dir")
-    a = ap.parse_args(argv)
-    from .common.tb_writer import encode_png
-    dec = AutoencoderDCDecoderHIP.from_pretrained(a.vae, device=a.device)
-    lats = torch.load(a.latents, map_location="cpu")
-    if isinstance(lats, torch.Tensor):
-        lats = list(lats.unsqueeze(1)) if lats.dim() == 4 else [lats]
-    os.makedirs(a.out_dir, exist_ok=True)
-    for idx, lat in enumerate(lats):
-        img = dec.to_uint8(dec.decode(lat if lat.dim() == 4 else lat[None]))[0].cpu()
-        path = os.path.join(a.out_dir, f"validation_{idx}.png")
-        with open(path, "wb") as f:
-            f.write(encode_png(img))
-        print(path)
+    latents_to_png_main("python -m yat_amd.dcae", "AutoencoderDC", AutoencoderDCDecoderHIP, argv)
 
 
 if __name__ == "__main__":

@@ -15,17 +15,18 @@ block or downsample type is refused]:
 
 Hot path: the down blocks, ``conv_out`` and the uint8 ingest are csrc/dcae_enc.hip; everything else is what the decoder
 runs on (csrc/dcae.hip, the GEMM family, yat_dwconv_glu_fwd, yat_linear_attn_fwd).
+
+Directory loading, the strict key check and the buffer cache: yat_amd/vae_common.py.
 """
 from __future__ import annotations
 
-import json
-import os
 from dataclasses import dataclass
 
 import torch
 
-from .dcae import (BF16, EVIT, HEAD, RES, _per_stage, alloc_buffers, block_keys, evit_block, pack_block, pack_conv3x3,
-                   res_block)
+from .dcae import (HEAD, RES, alloc_buffers, block_keys, evit_block, pack_block, parse_stages, refuse_quadratic_grids,
+                   res_block, validate_stages)
+from .vae_common import BF16, VAEHalfHIP, check_expected, load_tensors, pack_conv3x3, read_config
 
 IN_PAD = 8            # conv_in reads 8 input channels (Cin % 8 == 0 on the MFMA conv): RGB + 5 zero channels
 
@@ -52,19 +53,8 @@ class DCAEEncoderConfig:
 
 
 def parse_encoder_config(raw: dict) -> DCAEEncoderConfig:
-    """``vae/config.json`` (AutoencoderDC) -> the encoder's configuration.  Per-stage keys may be a scalar (every stage) or
-    a list (one entry per stage); ``encoder_qkv_multiscales`` a list of kernel sizes (every stage) or a list of lists."""
-    chans = tuple(int(c) for c in raw["encoder_block_out_channels"])
-    n = len(chans)
-    types = _per_stage(raw.get("encoder_block_types", RES), n, "encoder_block_types")
-    layers = tuple(int(v) for v in _per_stage(raw.get("encoder_layers_per_block", 2), n, "encoder_layers_per_block"))
-    ms = raw.get("encoder_qkv_multiscales", ())
-    if isinstance(ms, (list, tuple)) and ms and all(isinstance(m, (list, tuple)) for m in ms):
-        ms = tuple(tuple(int(k) for k in m) for m in _per_stage(list(ms), n, "encoder_qkv_multiscales"))
-    elif isinstance(ms, (list, tuple)):
-        ms = (tuple(int(k) for k in ms),) * n
-    else:
-        ms = ((int(ms),),) * n
+    """``vae/config.json`` (AutoencoderDC) -> the encoder's configuration (``dcae.parse_stages`` for the per-stage keys)."""
+    chans, types, layers, ms = parse_stages(raw, "encoder")
     if not raw.get("out_shortcut", True):
         raise NotImplementedError("out_shortcut false: the encoder without its conv_out shortcut is not built")
     cfg = DCAEEncoderConfig(
@@ -84,19 +74,7 @@ def _validate(cfg: DCAEEncoderConfig) -> None:
         raise NotImplementedError("encoder stage 0: 0 layers (diffusers then makes conv_in a down block, which is not built)")
     if cfg.in_channels > IN_PAD:
         raise NotImplementedError(f"{cfg.in_channels} input channels")
-    for i, (c, t, nl, ms) in enumerate(zip(cfg.block_out_channels, cfg.block_types, cfg.layers_per_block,
-                                           cfg.qkv_multiscales)):
-        if t not in (RES, EVIT):
-            raise NotImplementedError(f"encoder stage {i}: block type {t!r} (built: {RES}, {EVIT})")
-        if t == EVIT and (tuple(ms) != (5,) or cfg.attention_head_dim != HEAD):
-            raise NotImplementedError(f"encoder stage {i}: qkv_multiscales {ms} / head dim {cfg.attention_head_dim} "
-                                      f"(built: (5,) / {HEAD})")
-        if nl <= 0:
-            raise NotImplementedError(f"encoder stage {i}: {nl} layers (a stage without blocks is not built)")
-        if c % 8 or (t == EVIT and c % HEAD):
-            raise ValueError(f"encoder stage {i}: {c} channels")
-        if i + 1 < cfg.num_stages and (4 * c) % cfg.block_out_channels[i + 1]:
-            raise ValueError(f"encoder stage {i}: the down-block shortcut needs 4*{c} % {cfg.block_out_channels[i + 1]} == 0")
+    validate_stages(cfg, "encoder", "down")
     if cfg.block_out_channels[-1] % cfg.latent_channels or cfg.latent_channels % 4:
         raise ValueError(f"conv_out shortcut: {cfg.block_out_channels[-1]} % {cfg.latent_channels} != 0")
 
@@ -121,16 +99,8 @@ def expected_keys(cfg: DCAEEncoderConfig) -> dict:
 def check_state(cfg: DCAEEncoderConfig, sd: dict) -> None:
     """Strict load: every expected ``encoder.`` key present with its shape, and no other ``encoder.`` key (decoder keys are
     ignored).  Raises KeyError / ValueError naming the key."""
-    want = expected_keys(cfg)
-    for k, shape in want.items():
-        if k not in sd:
-            raise KeyError(f"DC-AE encoder weight {k!r} is missing from the checkpoint")
-        if tuple(sd[k].shape) != shape:
-            raise ValueError(f"DC-AE encoder weight {k!r} has shape {tuple(sd[k].shape)}, expected {shape}")
-    extra = sorted(k for k in sd if k.startswith("encoder.") and k not in want)
-    if extra:
-        raise KeyError(f"DC-AE encoder weight {extra[0]!r} is not consumed by the {cfg.block_types} encoder "
-                       f"({len(extra)} unconsumed key(s))")
+    check_expected(expected_keys(cfg), sd, lambda k: k.startswith("encoder."), "DC-AE encoder",
+                   f"the {cfg.block_types} encoder")
 
 
 def pad_conv_in(w: torch.Tensor) -> torch.Tensor:
@@ -160,15 +130,7 @@ def pack_weights(cfg: DCAEEncoderConfig, sd: dict) -> dict:
 
 def load_vae_dir(vae_dir: str):
     """(config, ``encoder.*`` tensors) of a diffusers AutoencoderDC directory."""
-    from safetensors import safe_open
-    with open(os.path.join(vae_dir, "config.json")) as f:
-        cfg = parse_encoder_config(json.load(f))
-    sd = {}
-    with safe_open(os.path.join(vae_dir, "diffusion_pytorch_model.safetensors"), framework="pt") as f:
-        for k in f.keys():
-            if k.startswith("encoder."):
-                sd[k] = f.get_tensor(k)
-    return cfg, sd
+    return parse_encoder_config(read_config(vae_dir)), load_tensors(vae_dir, lambda k: k.startswith("encoder."))
 
 
 def shortcut_gather_index(cin: int, cout: int):
@@ -179,44 +141,27 @@ def shortcut_gather_index(cin: int, cout: int):
     return u // 4, (u % 4) // 2, u % 2
 
 
-class AutoencoderDCEncoderHIP:
+class AutoencoderDCEncoderHIP(VAEHalfHIP):
     """The encoder half of AutoencoderDC in bf16 on the HIP kernels.  ``encode`` runs one image at a time on the current
     stream through activation buffers sized for the largest stage (kept between calls of the same image size).
 
     The reference encodes with ``vae.enable_tiling`` only at the 2048-px resolution (train_sana.py:56-57): at 2048 px and
     above its latent is stitched from tiles, so it differs from this untiled encode along the tile seams; below that both
     encode whole."""
-
-    def __init__(self, cfg: DCAEEncoderConfig, packed: dict, device="cuda"):
-        self.cfg = cfg
-        self.device = torch.device(device)
-        self.w = {k: v.to(self.device, BF16).contiguous() for k, v in packed.items()}
-        self._bufs = None
-
-    @classmethod
-    def from_pretrained(cls, vae_dir: str, device="cuda"):
-        cfg, sd = load_vae_dir(vae_dir)
-        return cls(cfg, pack_weights(cfg, sd), device)
+    load_vae_dir = staticmethod(load_vae_dir)
+    pack_weights = staticmethod(pack_weights)
 
     def _stage_sizes(self, H, W):
         return [(H >> i, W >> i) for i in range(self.cfg.num_stages)]
 
-    def _buffers(self, H, W):
-        if self._bufs is not None and self._bufs[0] == (H, W):
-            return self._bufs[1]
-        self._bufs = None
-        bufs = alloc_buffers(self._stage_sizes(H, W), self.cfg.block_out_channels, self.cfg.block_types, self.device)
-        self._bufs = ((H, W), bufs)
-        return bufs
+    def _alloc_buffers(self, H, W):
+        return alloc_buffers(self._stage_sizes(H, W), self.cfg.block_out_channels, self.cfg.block_types, self.device)
 
     def _check_size(self, H, W):
-        cfg, f = self.cfg, self.cfg.spatial_factor
+        f = self.cfg.spatial_factor
         if H <= 0 or W <= 0 or H % f or W % f:
             raise ValueError(f"image size {H}x{W}: height and width must be multiples of {f}")
-        for (hh, ww), t in zip(self._stage_sizes(H, W), cfg.block_types):
-            if t == EVIT and hh * ww <= cfg.attention_head_dim:
-                raise ValueError(f"a {hh}x{ww} grid switches diffusers' multiscale attention to its quadratic form "
-                                 "(h*w <= 32), which is not built")
+        refuse_quadratic_grids(self._stage_sizes(H, W), self.cfg)
 
     def _encode_one(self, x8, out, H, W):
         """x8: [H, W, 8] bf16 (channels >= in_channels zero) -> out: [H/f, W/f, latent] bf16."""
@@ -239,7 +184,12 @@ class AutoencoderDCEncoderHIP:
                 x, cur, other = y, other, cur
         ops.dcae_conv3x3_mean(x, self.w["conv_out.w"], out, 1, hh, ww, ch[-1], cfg.latent_channels, bias=self.w["conv_out.b"])
 
-    def _finish(self, lat):
+    def _encode_batch(self, x8, H, W):
+        """x8: [B, H, W, 8] bf16 -> [B, latent, H/f, W/f] bf16, multiplied by ``scaling_factor``."""
+        f = self.cfg.spatial_factor
+        lat = torch.empty(x8.shape[0], H // f, W // f, self.cfg.latent_channels, dtype=BF16, device=self.device)
+        for b in range(x8.shape[0]):
+            self._encode_one(x8[b], lat[b], H, W)
         # [B, h, w, latent] -> NCHW; .to(bf16) * scaling_factor as the reference's caller does it (train_sana.py:81-82)
         return lat.permute(0, 3, 1, 2).contiguous() * self.cfg.scaling_factor
 
@@ -253,13 +203,9 @@ class AutoencoderDCEncoderHIP:
             raise ValueError(f"images must be [B, {cfg.in_channels}, H, W], got {tuple(images.shape)}")
         B, _, H, W = images.shape
         self._check_size(H, W)
-        f = cfg.spatial_factor
         x8 = torch.zeros(B, H, W, IN_PAD, dtype=BF16, device=self.device)
         x8[..., :cfg.in_channels] = images.to(self.device, BF16).permute(0, 2, 3, 1)
-        lat = torch.empty(B, H // f, W // f, cfg.latent_channels, dtype=BF16, device=self.device)
-        for b in range(B):
-            self._encode_one(x8[b], lat[b], H, W)
-        return self._finish(lat)
+        return self._encode_batch(x8, H, W)
 
     def encode_uint8(self, image: torch.Tensor) -> torch.Tensor:
         """[H, W, 3] (or [B, H, W, 3]) uint8, as PIL hands it over -> the latent of ``encode`` on torchvision's
@@ -270,11 +216,6 @@ class AutoencoderDCEncoderHIP:
         if image.dtype != torch.uint8 or image.dim() not in (3, 4) or image.shape[-1] != 3:
             raise ValueError(f"image must be [H, W, 3] or [B, H, W, 3] uint8, got {tuple(image.shape)} {image.dtype}")
         u = (image if image.dim() == 4 else image[None]).to(self.device).contiguous()
-        B, H, W, _ = u.shape
+        _, H, W, _ = u.shape
         self._check_size(H, W)
-        f = self.cfg.spatial_factor
-        x8 = ops.dcae_image_from_uint8(u)
-        lat = torch.empty(B, H // f, W // f, self.cfg.latent_channels, dtype=BF16, device=self.device)
-        for b in range(B):
-            self._encode_one(x8[b], lat[b], H, W)
-        return self._finish(lat)
+        return self._encode_batch(ops.dcae_image_from_uint8(u), H, W)
