@@ -126,7 +126,7 @@ class FlatParamModule(nn.Module):
         self._offset = dict(zip([n for n, _ in specs], offs))
         self.grad_ready = None            # callable(bucket_index) set by HipDDP
         self.loss_ready = None            # callable(loss tensor) set by HipDDP: the device path reports its loss before the backward
-        self.adapters = None              # yat_amd.lokr.LoKrAdapters when the config asks for PEFT adapters
+        self.adapters = None              # an AdapterSet (yat_amd/adapters.py) when the config asks for PEFT adapters
         self.param_events = None          # set by FlatAdamW(overlap_update=True): one event per bucket
         self.accumulate_grads = False     # True on non-first micro-steps of gradient accumulation
         self._arena, self._chains, self._side = {}, {}, None

@@ -26,13 +26,12 @@ truth as the dense path, checked by the same oracle test in both modes.
 """
 from __future__ import annotations
 
-import json
 import math
-import os
 
 import torch
 
 from . import ops
+from .adapters import AdapterSet, DenseDelta, ModuleDropout, SlabColumns, adapted_linear, is_target  # noqa: F401
 
 BF16 = torch.bfloat16
 
@@ -58,59 +57,15 @@ def factorization(dimension: int, factor: int = -1):
     return m, n
 
 
-def is_target(module_name: str, targets) -> bool:
-    return any(module_name == t or module_name.endswith("." + t) for t in targets)
+class LoKrAdapters(ModuleDropout, DenseDelta, AdapterSet):
+    kind, needs_widths_of_8 = "LoKr", False
+    # peft factorises the CHANNEL counts of a k x k convolution and hangs the kernel on lokr_w2: not this layout
+    refuses_conv = " (e.g. 'net.0.proj' instead of 'proj')"
 
-
-class SlabColumns:
-    """Column slots of [rows, K] slabs for the small per-step products an adapter set hands to the base GEMMs as their second
-    operand (row stride K = the row stride of the x they are computed from).  Slabs are zero-filled, kept from step to step and
-    handed out in call order; ``restart()`` at the start of a step."""
-
-    def __init__(self, device):
-        self.device, self.slabs, self.next = device, {}, {}
-
-    def restart(self):
-        self.next = {}
-
-    def take(self, M, K, width):
-        slabs = self.slabs.setdefault(K, [])
-        i, col = self.next.get(K, (0, 0))
-        if col + width > K:
-            i, col = i + 1, 0
-        if i == len(slabs) or slabs[i].shape[0] < M:
-            buf = torch.zeros(M, K, dtype=BF16, device=self.device)
-            if i == len(slabs):
-                slabs.append(buf)
-            else:
-                slabs[i] = buf                                  # (a larger batch than any before: this step's earlier slots
-        self.next[K] = (i, col + width)                         #  live in the old buffer, which their views keep alive)
-        return slabs[i][:M, col:col + width]
-
-
-def adapted_linear(ad, x, w, bias=None, out=None, **ep):
-    """Linear of a (possibly adapted) target, the ``lin`` hook of the models: base_layer(x) + adapter(x) (peft's wrap).  An
-    adapter set that can hand its term over as the GEMM's second operand pair (``forward_pair``: the factored LoKr targets)
-    costs one launch; otherwise the term is computed first and folded in through the ``pre_add`` epilogue."""
-    if ad is None:
-        return ops.linear_fwd(x, w, bias, out=out, **ep)
-    pair = ad.forward_pair(x, w) if hasattr(ad, "forward_pair") else None
-    if pair == "plain":
-        return ops.linear_fwd(x, w, bias, out=out, **ep)
-    if pair is not None:
-        a2, b2, k2, group = pair
-        return ops.linear_fwd(x, w, bias, out=out, a2=a2, b2=b2, k2=k2, a2_group_n=group, **ep)
-    tmp = ad.forward_term(x, w)                                   # None: no adapter on this weight
-    if tmp is None:
-        return ops.linear_fwd(x, w, bias, out=out, **ep)
-    return ops.linear_fwd(x, w, bias, out=out, pre_add=tmp, **ep)
-
-
-class LoKrAdapters:
     def __init__(self, model, targets, r: int, alpha: float, module_dropout: float = 0.0, mode: str | None = None,
                  pair: bool = True):
-        self.model, self.r, self.alpha, self.scale = model, int(r), float(alpha), float(alpha) / int(r)
-        self.targets, self.module_dropout = list(targets), float(module_dropout)
+        self.r, self.alpha, self.scale = int(r), float(alpha), float(alpha) / int(r)
+        self.module_dropout = float(module_dropout)
         self.mode = mode or "factored"
         if self.mode not in ("factored", "dense"):
             raise ValueError(f"LoKr mode {self.mode!r}")
@@ -118,47 +73,8 @@ class LoKrAdapters:
         # factored targets in the forward: T1_flat P^T as the SECOND OPERAND PAIR of the base Linear's GEMM (one launch, no
         # [M, out] addend) instead of a GEMM of its own + the pre_add epilogue; see forward_pair()
         self.pair = bool(pair) and self.mode == "factored"
+        self._scan(model, targets)
         dev = model.flat_param.device
-        self.entries, off, segs = [], 0, [0]
-
-        def take(n):
-            nonlocal off
-            o = off
-            off += (n + 7) & ~7
-            segs.append(o + n)              # segment = the tensor itself (the pad belongs to nobody)
-            segs.append(off)
-            return o
-        base_ptr = model.flat_param.data_ptr()
-        for key, w in model.P.items():
-            if not key.endswith(".weight") or w.dim() < 2 or not is_target(key[:-7], self.targets):
-                continue
-            if w.dim() == 4 and w.shape[2] * w.shape[3] != 1:
-                # peft factorises the CHANNEL counts of a k x k convolution and hangs the kernel on lokr_w2: not this layout
-                raise NotImplementedError(f"{key}: LoKr on a {w.shape[2]}x{w.shape[3]} convolution is not built; name the "
-                                          f"linear targets more narrowly (e.g. 'net.0.proj' instead of 'proj')")
-            out_dim, in_dim = w.shape[0], w.numel() // w.shape[0]
-            (out_l, out_k), (in_m, in_n) = factorization(out_dim), factorization(in_dim)
-            if not (self.r < max(out_k, in_n) / 2):
-                raise NotImplementedError(f"{key}: full lokr_w2 (r >= max(out_k, in_n)/2) is not built")
-            e = dict(module=key[:-7], key=key, out=out_dim, inn=in_dim, out_l=out_l, out_k=out_k, in_m=in_m, in_n=in_n,
-                     w_off=(w.data_ptr() - base_ptr) // 2, o1=take(out_l * in_m), oa=take(out_k * self.r),
-                     ob=take(self.r * in_n), active=True, has_grad=False, steps=0)
-            e["span"] = (e["o1"], off)      # [o1, end of w2_b incl. pad): the entry's contiguous, 8-aligned parameter range
-            # factored application needs 16-byte rows in every small GEMM: in_n, in_m*R, out multiples of 8
-            e["factored"] = (self.mode == "factored" and in_n % 8 == 0 and in_n <= 128 and self.R <= 16 and out_dim % 8 == 0
-                             and out_k * self.R * 4 <= 65536)
-            self.entries.append(e)
-        if not self.entries:
-            raise ValueError("no module matches lora_target_modules")
-        self.numel_flat = off
-        self.flat_param = torch.zeros(off, dtype=BF16, device=dev)
-        self.flat_grad = torch.zeros(off, dtype=BF16, device=dev)
-        # zero-length segments are fine for the norm kernel; keep them strictly increasing by dropping duplicates
-        self.seg_start = torch.tensor(sorted(set(segs)), dtype=torch.int64)
-        self.bucket_bounds = [(0, off)]
-        self.param_events = None
-        self.grad_ready = None              # HipDDP hook: called once, after project()
-        self.active_override = None         # callable(module name) -> bool replacing the module-dropout draw (tests)
         R = self.R
         fact = [e for e in self.entries if e["factored"]]
         # dense-mode entries keep their delta_w in a shadow of the model's flat weights (allocated only when one exists)
@@ -177,7 +93,7 @@ class LoKrAdapters:
             for e, n in zip(fact, sizes):
                 k2 = e["in_m"] * R
                 if self.pair:
-                    e["P"] = flatP[e["w_off"]:e["w_off"] + e["out"] * e["inn"]].view(e["out"], e["inn"])[:, :k2]
+                    e["P"] = self._shadow(e, flatP)[:, :k2]
                 else:
                     e["P"] = flatP[o:o + n].view(e["out"], k2)
                 e["dP"] = flatdP[o:o + n].view(e["out"], k2)
@@ -196,31 +112,32 @@ class LoKrAdapters:
         o = 0
         for e, n in zip(self.entries, sizes):
             e["ws"], o = ws_all[o:o + n], o + n
-        self._lookup = {}
         self._slabs = SlabColumns(dev)                 # T1 of forward_pair(): columns of [rows, in] slabs
-        self.reset_parameters()
-        model.adapters = self
+        self._attach()
+
+    def _lay_out(self, key, w, out_dim, in_dim, off):
+        """w1 [out_l, in_m] | w2_a [out_k, r] | w2_b [r, in_n], each 8-element aligned."""
+        (out_l, out_k), (in_m, in_n) = factorization(out_dim), factorization(in_dim)
+        if not (self.r < max(out_k, in_n) / 2):
+            raise NotImplementedError(f"{key}: full lokr_w2 (r >= max(out_k, in_n)/2) is not built")
+        starts, ends = [], []
+        for n in (out_l * in_m, out_k * self.r, self.r * in_n):
+            starts.append(off)
+            ends.append(off + n)            # segment = the tensor itself (the pad belongs to nobody)
+            off += (n + 7) & ~7
+            ends.append(off)
+        # factored application needs 16-byte rows in every small GEMM: in_n, in_m*R, out multiples of 8
+        factored = (self.mode == "factored" and in_n % 8 == 0 and in_n <= 128 and self.R <= 16 and out_dim % 8 == 0
+                    and out_k * self.R * 4 <= 65536)
+        # span = [o1, end of w2_b incl. pad): the entry's contiguous, 8-aligned parameter range
+        return dict(out_l=out_l, out_k=out_k, in_m=in_m, in_n=in_n, o1=starts[0], oa=starts[1], ob=starts[2], active=True,
+                    has_grad=False, steps=0, span=(starts[0], off), factored=factored), ends
 
     # ---- views
     def _views(self, e, flat):
         return (flat[e["o1"]:e["o1"] + e["out_l"] * e["in_m"]].view(e["out_l"], e["in_m"]),
                 flat[e["oa"]:e["oa"] + e["out_k"] * self.r].view(e["out_k"], self.r),
                 flat[e["ob"]:e["ob"] + self.r * e["in_n"]].view(self.r, e["in_n"]))
-
-    def delta_like(self, w):
-        """The view of the delta buffer that mirrors weight view ``w`` (same offset, shape and strides)."""
-        off = (w.data_ptr() - self.model.flat_param.data_ptr()) // 2
-        return torch.as_strided(self.delta, w.size(), w.stride(), off)
-
-    def lookup(self, t, base):
-        """Adapter entries whose target weight lies inside ``t`` (a view of the model's flat parameter or gradient buffer
-        ``base``; a fused q|k|v view holds three) -> [(entry, first row of the target inside the view)]."""
-        off, n = (t.data_ptr() - base.data_ptr()) // 2, t.numel()
-        hit = self._lookup.get((off, n))
-        if hit is None:
-            hit = [(e, (e["w_off"] - off) // e["inn"]) for e in self.entries if off <= e["w_off"] < off + n]
-            self._lookup[(off, n)] = hit
-        return hit
 
     def _w2(self, e):
         """(w2_a [out_k, R], w2_b [R, in_n]) with the rank padded to R."""
@@ -245,8 +162,7 @@ class LoKrAdapters:
             if not e["active"]:
                 blk.zero_()
             elif not e["factored"]:
-                d = self.delta[e["w_off"]:e["w_off"] + e["out"] * e["inn"]].view(e["out"], e["inn"])
-                ops.gemm(x, d, blk, M=M, N=e["out"], K=e["inn"], ldc=rows)
+                self._dense_forward(e, x, blk, rows)
             else:
                 im, n_ = e["in_m"], e["in_n"]
                 t1 = ops.lokr_rows_fwd(x.view(M * im, n_), self._w2(e)[1], torch.empty(M * im, R, dtype=BF16, device=x.device))
@@ -310,8 +226,7 @@ class LoKrAdapters:
                 continue
             dyb = dy[:, row0:row0 + e["out"]]
             if not e["factored"]:
-                d = self.delta[e["w_off"]:e["w_off"] + e["out"] * e["inn"]].view(e["out"], e["inn"])
-                ops.gemm(dyb, d, dx, b_t=True, M=M, N=e["inn"], K=e["out"], lda=ld, ldb=e["inn"], ldc=e["inn"], residual=dx)
+                self._dense_dgrad(e, dyb, dx)
                 continue
             im, n_ = e["in_m"], e["in_n"]
             h = torch.empty(M, im * R, dtype=BF16, device=dy.device)
@@ -330,17 +245,15 @@ class LoKrAdapters:
         for e, row0 in self.lookup(gw, self.model.flat_grad):
             if not e["active"]:
                 continue
-            # gradient accumulation x module dropout: an entry dropped on the earlier micro-steps of this window holds
-            # the PREVIOUS window's sums in d_P / d_w2_b / its dense slot -- its first active micro-step overwrites
-            accumulate = acc_all and e["has_grad"]
-            e["has_grad"] = True
             dyb = dy[:, row0:row0 + e["out"]]
             if not e["factored"]:
-                g = self.model.flat_grad[e["w_off"]:e["w_off"] + e["out"] * e["inn"]].view(e["out"], e["inn"])
-                ops.gemm(dyb, x, g, a_t=True, b_t=True, M=e["out"], N=e["inn"], K=M, lda=ld, ldb=e["inn"], ldc=e["inn"],
-                         residual=g if accumulate else None)
+                self._dense_wgrad(e, dyb, x, acc_all)
                 self._project_entry(e)
                 continue
+            # gradient accumulation x module dropout, as in _dense_wgrad(): an entry dropped on the earlier micro-steps of
+            # this window holds the PREVIOUS window's sums in d_P / d_w2_b -- its first active micro-step overwrites
+            accumulate = acc_all and e["has_grad"]
+            e["has_grad"] = True
             im, n_ = e["in_m"], e["in_n"]
             x2 = x.view(M * im, n_)
             kept = e.get("t1")
@@ -372,26 +285,14 @@ class LoKrAdapters:
                 torch.nn.init.kaiming_uniform_(init, a=math.sqrt(5))
                 t.copy_(init.to(BF16))
 
-    def join_pending_update(self):
-        pev, self.param_events = self.param_events, None
-        if pev is not None:
-            cur = torch.cuda.current_stream()
-            for ev in pev:
-                cur.wait_event(ev)
-
     # ---- per step
     def materialize(self, training=True):
         """Rebuild every delta_w from the current adapter parameters (zeros where module dropout drops the adapter)."""
         self.join_pending_update()
         self._slabs.restart()               # this step's T1 products take the slab columns from the start again
-        first_micro = not getattr(self.model, "accumulate_grads", False)
+        self._draw_active(training)
         for e in self.entries:
             e["projected"] = False
-            if first_micro:
-                e["has_grad"] = False       # a new accumulation window: nothing has contributed yet
-            e["active"] = (not training) or self.module_dropout <= 0.0 or bool(torch.rand(1) > self.module_dropout)
-            if training and self.active_override is not None:     # tests: a chosen drop pattern instead of the draw
-                e["active"] = bool(self.active_override(e["module"]))
             w1, wa, wb = self._views(e, self.flat_param)
             if e["factored"]:
                 if e["active"]:
@@ -400,7 +301,7 @@ class LoKrAdapters:
                         e["wb_pad"][:self.r].copy_(wb)
                     ops.lokr_delta(w1, self._w2(e)[0], self._eye, self.scale, e["P"])      # kron(w1, w2_a) * scale
                 continue
-            d2 = self.delta[e["w_off"]:e["w_off"] + e["out"] * e["inn"]].view(e["out"], e["inn"])
+            d2 = self._shadow(e, self.delta)
             if e["active"]:
                 ops.lokr_delta(w1, wa, wb, self.scale, d2)
             else:
@@ -420,8 +321,7 @@ class LoKrAdapters:
                 continue
             if not e.get("projected"):      # (wgrad() projects an entry right behind its weight gradient)
                 self._project_entry(e)
-        if self.grad_ready is not None:
-            self.grad_ready(0)
+        super().project()
 
     def _project_entry(self, e):
         """Entry e's d_P (factored) / d_delta_w (dense) -> (d_w1, d_w2_a[, d_w2_b]) on the current stream.  Idempotent: under
@@ -435,26 +335,8 @@ class LoKrAdapters:
             if ga_r is not ga:
                 ga.copy_(ga_r[:, :self.r])
         else:
-            dd = self.model.flat_grad[e["w_off"]:e["w_off"] + e["out"] * e["inn"]].view(e["out"], e["inn"])
-            ops.lokr_project(w1, wa, wb, self.scale, dd, g1, ga, gb, e["ws"])
+            ops.lokr_project(w1, wa, wb, self.scale, self._shadow(e, self.model.flat_grad), g1, ga, gb, e["ws"])
         e["projected"] = True
-
-    def update_ranges(self):
-        """Parameter ranges the optimizer step must touch, with each range's own step count: [(lo, hi, step)].  peft leaves
-        a dropped adapter's ``.grad`` None, so torch.optim.AdamW skips it altogether -- no parameter, moment or weight-decay
-        update, and its per-parameter ``step`` (the bias correction) does not advance.  Entries are contiguous in the flat
-        buffer; neighbours with the same count share a launch."""
-        out = []
-        for e in self.entries:
-            if not e["has_grad"]:
-                continue
-            e["steps"] += 1
-            lo, hi = e["span"]
-            if out and out[-1][1] == lo and out[-1][2] == e["steps"]:
-                out[-1] = (out[-1][0], hi, e["steps"])
-            else:
-                out.append((lo, hi, e["steps"]))
-        return out
 
     # ---- checkpoint (peft layout: adapter_model.safetensors + adapter_config.json)
     def state_dict(self):
@@ -462,25 +344,20 @@ class LoKrAdapters:
         sd = {}
         for e in self.entries:
             w1, wa, wb = self._views(e, self.flat_param)
-            pre = f"base_model.model.{e['module']}."
+            pre = self._peft_prefix(e)
             sd[pre + "lokr_w1"], sd[pre + "lokr_w2_a"], sd[pre + "lokr_w2_b"] = w1, wa, wb
         return sd
 
     def load_state_dict(self, sd):
         for e in self.entries:
-            pre = f"base_model.model.{e['module']}."
+            pre = self._peft_prefix(e)
             for t, name in zip(self._views(e, self.flat_param), ("lokr_w1", "lokr_w2_a", "lokr_w2_b")):
                 t.copy_(sd[pre + name].to(device=t.device, dtype=BF16))
 
-    def save_pretrained(self, path):
-        from safetensors.torch import save_file
-        os.makedirs(path, exist_ok=True)
-        save_file({k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()},
-                  os.path.join(path, "adapter_model.safetensors"))
-        with open(os.path.join(path, "adapter_config.json"), "w") as f:
-            json.dump({"peft_type": "LOKR", "r": self.r, "alpha": self.alpha, "module_dropout": self.module_dropout,
-                       "target_modules": self.targets, "decompose_both": False, "decompose_factor": -1,
-                       "init_weights": True, "rank_dropout": 0.0, "use_effective_conv2d": False}, f, indent=2)
+    def _peft_config(self):
+        return {"peft_type": "LOKR", "r": self.r, "alpha": self.alpha, "module_dropout": self.module_dropout,
+                "target_modules": self.targets, "decompose_both": False, "decompose_factor": -1,
+                "init_weights": True, "rank_dropout": 0.0, "use_effective_conv2d": False}
 
     def num_parameters(self):
         return sum(e["out_l"] * e["in_m"] + e["out_k"] * self.r + self.r * e["in_n"] for e in self.entries)

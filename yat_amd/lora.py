@@ -7,7 +7,7 @@ Linear / 1x1 Conv with weight W [out, in]:
     result = base_layer(x) + lora_B(lora_A(dropout(x))) * scaling,   scaling = lora_alpha / r
 with lora_A [r, in] kaiming-uniform(a=sqrt(5)), lora_B [out, r] zeros, every op in the module dtype (bf16).
 
-MI355X mapping (same interface as yat_amd/lokr.py, so yat_amd/sana.py's hooks do not change): the adapter set owns one flat
+MI355X mapping (an ``AdapterSet`` of yat_amd/adapters.py, so the models' hooks do not change): the adapter set owns one flat
 bf16 buffer (per target: A [R, in] then B^T [R, out], R = the rank padded to 8 so every skinny GEMM keeps 16-byte rows; the
 padding rows stay exactly zero: their gradients are zero) with a flat gradient twin -- clip + AdamW and the data-parallel
 all-reduce are the usual single launches.  Per target and step:
@@ -23,56 +23,33 @@ Philox stream, the arithmetic (x * mask / (1 - p), one rounding) does.  DoRA is 
 """
 from __future__ import annotations
 
-import json
 import math
-import os
 
 import torch
 
 from . import ops
-from .lokr import is_target, SlabColumns
+from .adapters import AdapterSet, SlabColumns
 
 BF16 = torch.bfloat16
 
 
-class LoRAAdapters:
+class LoRAAdapters(AdapterSet):
+    kind = "LoRA"
+
     def __init__(self, model, targets, r: int, alpha: float, dropout: float = 0.0, use_rslora: bool = False, seed: int = 0,
                  pair: bool = True):
         if not (0.0 <= float(dropout or 0.0) < 1.0):
             raise ValueError("lora_dropout must be in [0, 1)")
-        self.model, self.r, self.alpha, self.use_rslora = model, int(r), float(alpha), bool(use_rslora)
+        self.r, self.alpha, self.use_rslora = int(r), float(alpha), bool(use_rslora)
         self.dropout, self._seed, self._step = float(dropout or 0.0), int(seed), 0
         # [RECALL peft] scaling = lora_alpha / r, or lora_alpha / sqrt(r) with use_rslora
         self.scale = float(alpha) / (math.sqrt(int(r)) if use_rslora else int(r))
-        self.targets = list(targets)
         self.R = R = (self.r + 7) // 8 * 8
         if R > 16:
             raise NotImplementedError("LoRA rank > 16")
+        self._scan(model, targets)
         dev = model.flat_param.device
-        self.entries, off, segs = [], 0, [0]
-        base_ptr = model.flat_param.data_ptr()
-        for key, w in model.P.items():
-            if not key.endswith(".weight") or w.dim() < 2 or not is_target(key[:-7], self.targets):
-                continue
-            out_dim, in_dim = w.shape[0], w.numel() // w.shape[0]
-            if out_dim % 8 or in_dim % 8:
-                raise NotImplementedError(f"{key}: LoRA needs layer widths that are multiples of 8")
-            e = dict(module=key[:-7], key=key, out=out_dim, inn=in_dim, w_off=(w.data_ptr() - base_ptr) // 2,
-                     oa=off, ob=off + R * in_dim, active=True, index=len(self.entries))
-            off += R * (in_dim + out_dim)
-            segs += [e["ob"], off]
-            self.entries.append(e)
-        if not self.entries:
-            raise ValueError("no module matches lora_target_modules")
-        self.numel_flat = off
-        self.flat_param = torch.zeros(off, dtype=BF16, device=dev)
-        self.flat_grad = torch.zeros(off, dtype=BF16, device=dev)
-        self.seg_start = torch.tensor(sorted(set(segs)), dtype=torch.int64)
-        self.bucket_bounds = [(0, off)]
-        self.param_events = None
-        self.grad_ready = None
         self._gate = torch.full((max(max(e["out"] for e in self.entries), R),), self.scale, dtype=BF16, device=dev)
-        self._lookup = {}
         # forward through the base GEMM's second operand pair (forward_pair()): scaling * lora_B of every adapter in the first R
         # columns of its target's rows of a zero-filled shadow of the flat weights, rebuilt by one launch per step; T in slab columns
         # (per target: 64 columns must fit a row, and the rows of the shadow must be 16-byte aligned)
@@ -85,8 +62,11 @@ class LoRAAdapters:
             self._slabs = SlabColumns(dev)
             self._b_table = torch.tensor([[e["ob"], e["w_off"], e["out"], e["inn"]] for e in paired], dtype=torch.int64).to(dev)
             self._n_paired, self._max_out = len(paired), max(e["out"] for e in paired)
-        self.reset_parameters()
-        model.adapters = self
+        self._attach()
+
+    def _lay_out(self, key, w, out_dim, in_dim, off):
+        ob = off + self.R * in_dim
+        return dict(oa=off, ob=ob, index=len(self.entries)), [ob, ob + self.R * out_dim]
 
     # ---- views: A [R, in] (rows >= r zero), B^T [R, out] (rows >= r zero)
     def _views(self, e, flat):
@@ -102,22 +82,7 @@ class LoRAAdapters:
             torch.nn.init.kaiming_uniform_(init, a=math.sqrt(5))
             a[:self.r].copy_(init.to(BF16))
 
-    def join_pending_update(self):
-        pev, self.param_events = self.param_events, None
-        if pev is not None:
-            cur = torch.cuda.current_stream()
-            for ev in pev:
-                cur.wait_event(ev)
-
-    def lookup(self, t, base):
-        off, n = (t.data_ptr() - base.data_ptr()) // 2, t.numel()
-        hit = self._lookup.get((off, n))
-        if hit is None:
-            hit = [(e, (e["w_off"] - off) // e["inn"]) for e in self.entries if off <= e["w_off"] < off + n]
-            self._lookup[(off, n)] = hit
-        return hit
-
-    # ---- per step (interface of yat_amd/lokr.py)
+    # ---- per step (the hooks of yat_amd/adapters.py)
     def materialize(self, training=True):
         self.join_pending_update()
         if self.pair:                              # b2 of every target for this step; T takes the slab columns from the start
@@ -152,7 +117,7 @@ class LoRAAdapters:
         return tmp
 
     def forward_pair(self, x, w):
-        """The adapter term of target view ``w`` as the second operand pair of the base GEMM (interface of yat_amd/lokr.py):
+        """The adapter term of target view ``w`` as the second operand pair of the base GEMM (for ``adapted_linear``):
         a2 = T = dropout(x) A^T in the first R of 64 slab columns per adapter (row stride of x), b2 = scaling * lora_B in the
         shadow of the weights, k2 = 64.  base + adapter is accumulated in fp32 and rounded once (peft rounds u, u * scaling and
         the sum; with scaling a power of two the products are the same numbers)."""
@@ -218,36 +183,27 @@ class LoRAAdapters:
             ops.lokr_small_wgrad(t, dyb, gbt[:self.r], accumulate=accumulate, scale=self.scale)   # d_B^T = scaling T^T dy
             ops.lokr_small_wgrad(dt, self._dropped(e, x), ga[:self.r], accumulate=accumulate)     # d_A = dT^T dropout(x)
 
-    def project(self):
-        if self.grad_ready is not None:            # gradients are complete as written; only the DDP hook remains
-            self.grad_ready(0)
-
     # ---- checkpoint (peft layout)
     def state_dict(self):
         self.join_pending_update()
         sd = {}
         for e in self.entries:
             a, bt = self._views(e, self.flat_param)
-            pre = f"base_model.model.{e['module']}."
+            pre = self._peft_prefix(e)
             sd[pre + "lora_A.weight"], sd[pre + "lora_B.weight"] = a[:self.r], bt[:self.r].t()
         return sd
 
     def load_state_dict(self, sd):
         for e in self.entries:
             a, bt = self._views(e, self.flat_param)
-            pre = f"base_model.model.{e['module']}."
+            pre = self._peft_prefix(e)
             a[:self.r].copy_(sd[pre + "lora_A.weight"].to(device=a.device, dtype=BF16).view(self.r, e["inn"]))
             bt[:self.r].copy_(sd[pre + "lora_B.weight"].to(device=a.device, dtype=BF16).view(e["out"], self.r).t())
 
-    def save_pretrained(self, path):
-        from safetensors.torch import save_file
-        os.makedirs(path, exist_ok=True)
-        save_file({k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()},
-                  os.path.join(path, "adapter_model.safetensors"))
-        with open(os.path.join(path, "adapter_config.json"), "w") as f:
-            json.dump({"peft_type": "LORA", "r": self.r, "lora_alpha": self.alpha, "lora_dropout": self.dropout,
-                       "target_modules": self.targets, "use_dora": False, "use_rslora": self.use_rslora, "bias": "none",
-                       "init_lora_weights": True}, f, indent=2)
+    def _peft_config(self):
+        return {"peft_type": "LORA", "r": self.r, "lora_alpha": self.alpha, "lora_dropout": self.dropout,
+                "target_modules": self.targets, "use_dora": False, "use_rslora": self.use_rslora, "bias": "none",
+                "init_lora_weights": True}
 
     def num_parameters(self):
         return sum(self.r * (e["inn"] + e["out"]) for e in self.entries)

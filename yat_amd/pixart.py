@@ -16,7 +16,7 @@ gradients and the text branch on a second stream).  What differs from SANA is on
 * attn2 reads the projected captions directly (no RMSNorm), T = 300 padded keys;
 * the FFN is Linear(D, 4D) -> GELU(tanh) -> Linear(4D, D): two GEMMs with fused bias+activation / bias+gate+residual epilogues;
 * the head emits 2C channels (learned sigma); unpatchify is ``yat_patch_rearrange`` in the "nhwpqc" order.
-PEFT adapters (yat_amd/lora.py, yat_amd/lokr.py) hook in exactly as in yat_amd/sana.py: ``lin`` / ``dgrad`` / ``wgrad``.
+PEFT adapters (yat_amd/adapters.py and its four kinds) hook in exactly as in yat_amd/sana.py: ``lin`` / ``dgrad`` / ``wgrad``.
 """
 from __future__ import annotations
 
@@ -29,7 +29,7 @@ import torch
 
 from . import ops
 from .flat import FlatParamModule, schedule
-from .lokr import adapted_linear
+from .adapters import PendingWgrads, adapted_linear
 
 BF16 = torch.bfloat16
 
@@ -225,7 +225,7 @@ class PixArtTransformer2DModelHIP(FlatParamModule):
         cfg, P = self.cfg, self.P
         ad = self.adapters
         if ad is not None:
-            ad.materialize(self.training)                     # yat_amd/lora.py / lokr.py: this step's adapter state
+            ad.materialize(self.training)                     # yat_amd/adapters.py: this step's adapter state
         D, H, dh, p = cfg.inner_dim, cfg.num_attention_heads, cfg.attention_head_dim, cfg.patch_size
         B, Cin, Hl, Wl = latents.shape
         if Hl % p or Wl % p:
@@ -411,19 +411,12 @@ class PixArtTransformer2DModelHIP(FlatParamModule):
         side = self._side_stream() if self.side_wgrad else None
         aux = self._chain_stream(1) if (side is not None and self.aux_colsum and ad is None) else None
         aux_used = [False]
-        pending_ad = []                   # adapter weight gradients wait for the H product of the dgrad of the same dy
+        pending_ad = PendingWgrads(ad, acc)   # adapter weight gradients wait for the H product of the dgrad of the same dy
 
         def dgrad(dy_, w_, out=None, residual=None):
             r_ = ops.linear_dgrad(dy_, w_, out=out, residual=residual)
             if ad is not None:
-                hs = ad.dgrad_term(dy_, w_, r_)
-                keep = []
-                for item in pending_ad:
-                    if item[0].data_ptr() == dy_.data_ptr():
-                        off_chain(lambda item=item, hs=hs: ad.wgrad(*item, accumulate=acc, hs=hs))
-                    else:
-                        keep.append(item)
-                pending_ad[:] = keep
+                pending_ad.flush(dy_, ad.dgrad_term(dy_, w_, r_), off_chain)
             return r_
 
         def off_chain(fn):
@@ -439,7 +432,7 @@ class PixArtTransformer2DModelHIP(FlatParamModule):
         def wgrad(dy, x, gw, gbias=None, dgrad_follows=True):
             if ad is not None:            # frozen base: only the adapters' share, launched by the dgrad() of the same dy
                 if dgrad_follows:
-                    pending_ad.append((dy, x, gw))
+                    pending_ad.add(dy, x, gw)
                 else:
                     off_chain(lambda: ad.wgrad(dy, x, gw, accumulate=acc))
                 return

@@ -38,7 +38,7 @@ import torch.nn as nn
 
 from . import ops
 from .flat import FlatParamModule, schedule
-from .lokr import adapted_linear
+from .adapters import PendingWgrads, adapted_linear
 
 BF16 = torch.bfloat16
 
@@ -293,7 +293,7 @@ class SanaTransformer2DModelHIP(FlatParamModule):
         ops.gemm_concurrency(2 if self.side_wgrad else 1)
         ad = self.adapters
         if ad is not None:
-            ad.materialize(self.training)                     # delta_w of every target for this step (yat_amd/lokr.py)
+            ad.materialize(self.training)                     # this step's adapter state (yat_amd/adapters.py)
 
         def lin(x_, w_, bias_=None, out=None, **ep):
             """Linear of a (possibly adapted) target: with adapters, x delta_w^T is computed first and folded into the
@@ -490,22 +490,12 @@ class SanaTransformer2DModelHIP(FlatParamModule):
             """Input gradient through a (possibly adapted) target: dy W, plus dy delta_w accumulated in place."""
             r_ = ops.linear_dgrad(dy_, w_, out=out, residual=residual)
             if ad is not None:
-                flush_adapter_wgrads(dy_, ad.dgrad_term(dy_, w_, r_))
+                pending_ad.flush(dy_, ad.dgrad_term(dy_, w_, r_), run_off_chain)
             return r_
 
         # With adapters the weight gradient of a target needs H = dy P, which the input gradient of the same dy computes
         # anyway: emit() only queues (dy, x, dW); the dgrad() that follows launches the queued item with its H.
-        pending_ad = []
-
-        def flush_adapter_wgrads(dy_=None, hs=None):
-            keep = []
-            for item in pending_ad:
-                if dy_ is None or item[0].data_ptr() == dy_.data_ptr():
-                    run_off_chain(lambda item=item, hs=(hs if dy_ is not None else None):
-                                  ad.wgrad(*item, accumulate=acc, hs=hs))
-                else:
-                    keep.append(item)
-            pending_ad[:] = keep
+        pending_ad = PendingWgrads(ad, acc)
 
         # Weight/bias gradients are off the critical path (nothing in backward reads them): they go to a second
         # stream so their blocks fill the CUs the single-round dgrad launches leave idle, and their prologue/epilogue
@@ -583,7 +573,7 @@ class SanaTransformer2DModelHIP(FlatParamModule):
                 """``text``: the reduction runs over the (packed) text rows -- never grouped, its K is the plan's dynamic
                 row count"""
                 if ad is not None:        # frozen base: adapter gradients only, launched by the dgrad() of the same dy
-                    pending_ad.append((dy_, x_, gw_))
+                    pending_ad.add(dy_, x_, gw_)
                     return
                 if group and self.group_small_wgrad:      # (also without a side stream: one launch instead of three
                     small.append((dy_, x_, gw_, bias))            #  split-K ones -- the serialized pass runs the step's kernels)
@@ -700,7 +690,7 @@ class SanaTransformer2DModelHIP(FlatParamModule):
                     dgrad(dkv2, wkv, out=denc, residual=None if first else denc)
 
             if ad is not None:
-                flush_adapter_wgrads()        # anything queued whose dy had no dgrad() (none today; keeps the queue per block)
+                pending_ad.flush(None, None, run_off_chain)   # anything whose dy had no dgrad() (none today; keeps the queue per block)
             if side is None:
                 block_grads()
                 if self.grad_ready is not None:

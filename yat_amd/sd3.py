@@ -32,7 +32,7 @@ import torch
 
 from . import ops
 from .flat import FlatParamModule, schedule
-from .lokr import adapted_linear
+from .adapters import PendingWgrads, adapted_linear
 
 BF16 = torch.bfloat16
 
@@ -231,7 +231,7 @@ class SD3Transformer2DModelHIP(FlatParamModule):
         cfg, P = self.cfg, self.P
         ad = self.adapters
         if ad is not None:
-            ad.materialize(self.training)                     # yat_amd/lora.py / lokr.py / loha.py: this step's adapter state
+            ad.materialize(self.training)                     # yat_amd/adapters.py: this step's adapter state
         D, H, dh, p = cfg.inner_dim, cfg.num_attention_heads, cfg.attention_head_dim, cfg.patch_size
         B, Cin, Hl, Wl = latents.shape
         if Hl % p or Wl % p:
@@ -482,12 +482,12 @@ class SD3Transformer2DModelHIP(FlatParamModule):
                 fn()
 
         ad = self.adapters
-        pending_ad = []                   # adapter weight gradients wait for the H product of the dgrad of the same dy
+        pending_ad = PendingWgrads(ad, acc)   # adapter weight gradients wait for the H product of the dgrad of the same dy
 
         def wgrad(dy, x, gw, gbias=None, dgrad_follows=True):
             if ad is not None:            # frozen base: only the adapters' share, launched by the dgrad() of the same dy
                 if dgrad_follows:
-                    pending_ad.append((dy, x, gw))
+                    pending_ad.add(dy, x, gw)
                 else:
                     off_chain(lambda: ad.wgrad(dy, x, gw, accumulate=acc))
                 return
@@ -499,14 +499,7 @@ class SD3Transformer2DModelHIP(FlatParamModule):
         def dgrad(dy_, w_, out=None, residual=None):
             r_ = ops.linear_dgrad(dy_, w_, out=out, residual=residual)
             if ad is not None:
-                hs = ad.dgrad_term(dy_, w_, r_)
-                keep = []
-                for item in pending_ad:
-                    if item[0].data_ptr() == dy_.data_ptr():
-                        off_chain(lambda item=item, hs=hs: ad.wgrad(*item, accumulate=acc, hs=hs))
-                    else:
-                        keep.append(item)
-                pending_ad[:] = keep
+                pending_ad.flush(dy_, ad.dgrad_term(dy_, w_, r_), off_chain)
             return r_
         # d(silu(temb)): every modulation Linear adds its share (bf16 accumulation, as autograd sums the bf16 branches);
         # lives on the second stream (the modulation gradients are produced there)
@@ -519,7 +512,7 @@ class SD3Transformer2DModelHIP(FlatParamModule):
             if ad is None:
                 ops.linear_wgrad(d_b, S.se, G[wkey], accumulate=acc, bias_grad=G[bkey], colsum_ws=ws_col)
             else:
-                pending_ad.append((d_b, S.se, G[wkey]))
+                pending_ad.add(d_b, S.se, G[wkey])
             dgrad(d_b, P[wkey], out=dse, residual=dse if dse_started[0] else None)
             dse_started[0] = True
 
