@@ -533,6 +533,32 @@ int yat_vae_attn_fwd(int B, int N, int dh, const void* q, const void* k, const v
                      yat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * AutoencoderKL encoder (diffusers AutoencoderKL, encoder only): the VAE encode of the PixArt-Sigma and SD3.5 feature
+ * extraction,  vae.encode(images).latent_dist.sample() [- shift_factor] * scaling_factor   train_pixart_sigma.py:61-66,
+ * train_sd35.py:63-77, with the VAE in bf16.  Activations are NHWC bf16; every call only enqueues work.  conv_in, the
+ * ResnetBlock2D convs and conv_out run on yat_dcae_conv3x3, GroupNorm (+ SiLU) and the mid-block attention on the decoder's
+ * entry points above, conv_shortcut / to_q|to_k|to_v / to_out.0 / quant_conv on yat_gemm_bf16_ex and the uint8 ingest on
+ * yat_dcae_image_from_uint8 (yat_amd/autoencoder_kl_encoder.py); the entry points below are what those do not cover.
+ *
+ * yat_vae_conv3x3_down: Downsample2D of DownEncoderBlock2D: F.pad(x, (0, 1, 0, 1)) -> nn.Conv2d(Cin, Cout, 3, stride=2,
+ *   padding=0), y = bf16(conv + bias): output pixel (oy, ox) reads input pixels (2 oy + ty, 2 ox + tx), ty, tx in 0..2, and
+ *   only the row below and the column right of the image are zeros (yat_dcae_conv3x3_down reads (2 oy + ty - 1, 2 ox + tx -
+ *   1): a different conv).  x: [B, H, W, Cin], H and W even; w: [Cout, 3, 3, Cin]; bias [Cout] or NULL; y: [B, H/2, W/2,
+ *   Cout].  Cin % 8 == 0, Cout % 4 == 0; the input must be < 2 GiB.
+ * yat_vae_kl_sample: DiagonalGaussianDistribution(moments).sample() (noise != NULL) or .mode() (noise == NULL), then the
+ *   trainers' shift and scale.  moments: [B, HW, ld] (NHWC rows of quant_conv's output), columns 0 .. L-1 the mean, L ..
+ *   2L-1 the logvar; noise, out: [B, L, HW] (NCHW).  fp32 arithmetic on bf16 values, one rounding per torch op of the bf16
+ *   module (a python-float operand enters as (float)value, as torch does it):
+ *     lv = clamp(logvar, -30, 20);  std = bf16(exp(bf16(0.5 * lv)));  x = bf16(mean + bf16(std * noise))   (.mode(): x = mean)
+ *     apply_shift = 1: x = bf16(x - shift);    out = bf16(x * scale)
+ *   L % 4 == 0; ld % 8 == 0, ld >= 2 L; moments 16-byte aligned; B * HW * ld < 2^31.  No atomics.
+ * ------------------------------------------------------------------------------------------ */
+int yat_vae_conv3x3_down(int B, int H, int W, int Cin, int Cout, const void* x, const void* w, const void* bias, void* y,
+                         yat_stream_t stream);
+int yat_vae_kl_sample(int B, int HW, int L, int ld, const void* moments, const void* noise, int apply_shift, float shift,
+                      float scale, void* out, yat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * launch plans: replay a recorded sequence of entry-point calls and stream / event operations in ONE call.
  * A training step over the same buffers issues the same ~900 launches and ~500 stream / event operations every time
  * (yat_amd/flat.py records them); replaying the list from C costs ~1 us per entry instead of a host-language call each.

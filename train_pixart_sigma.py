@@ -6,9 +6,11 @@ train_pixart_sigma.py:187-198), driving the MI355X-native path (BASELINE config 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train_pixart_sigma.py --config config.yaml
 
 ``pretrained_model_path`` (or ``pretrained_pipe_path``/transformer) must be a LOCAL diffusers directory; with neither the
-PixArt-Sigma-XL-2 architecture is random-initialised (no network here).  VAE / T5 feature extraction is outside the hot-path
-scope: training consumes cached-feature shards; validation samples latents from cached prompt embeddings and, when
-``<pretrained_pipe_path>/vae`` holds the AutoencoderKL, decodes them to images on the HIP decoder (yat_amd/autoencoder_kl.py).
+PixArt-Sigma-XL-2 architecture is random-initialised (no network here).  T5 text encoding and the ``extract_features`` loop
+are outside the hot-path scope: training consumes cached-feature shards (``python -m yat_amd.extract_latents`` makes their
+latents on the HIP AutoencoderKL encoder, which ``extract_latents`` also uses); validation samples latents from cached prompt
+embeddings and, when ``<pretrained_pipe_path>/vae`` holds the AutoencoderKL, decodes them to images on the HIP decoder
+(yat_amd/autoencoder_kl.py).
 
 Reference quirk: ``PixartSigmaTrainer.optimize(self, latents, embeddings)`` (:151) still has the two-argument signature
 while ``Model.run`` calls ``optimize(ratio, latents, embeddings, repa_features, generator)`` (common/trainer.py:337) -- at
@@ -23,7 +25,7 @@ import torch
 
 from yat_amd.common.training_parameters_reader import TrainingParameters
 from yat_amd.common.trainer import Model
-from yat_amd.autoencoder_kl import decode_validation, load_vae_decoder
+from yat_amd.autoencoder_kl import decode_validation, load_vae_decoder, load_vae_encoder
 from yat_amd.common.aspect_ratios import table_for_resolution
 from yat_amd.pixart import PixArtConfig, PixArtTransformer2DModelHIP
 from yat_amd.recipe import PixArtRecipe
@@ -60,11 +62,21 @@ class PixartSigmaTrainer(Model):
         self.aspect_ratios = table_for_resolution(self.model.config.sample_size * vae_compression)
         self.recipe = PixArtRecipe(self.model, self.scheduler, pad_to=300, device=dev)
         self.pipe = None
-        self.vae_dir = find_vae_dir(params.pretrained_pipe_path)                              # decoder only
+        self.vae_dir = find_vae_dir(params.pretrained_pipe_path)
         self.vae = None                                                                        # built at the first validate()
+        self.vae_encoder = None                                                                # built at the first extract_latents()
 
     def extract_latents(self, images):
-        raise NotImplementedError("VAE encoding is outside the hot-path scope; train from cached-feature shards")
+        """train_pixart_sigma.py:61-66 on the HIP AutoencoderKL encoder (yat_amd/autoencoder_kl_encoder.py), built from
+        ``<pretrained_pipe_path>/vae`` at the first call: ``vae.encode(images).latent_dist.sample() * scaling_factor``, never a
+        shift; the sample's noise comes from the device's global generator, as there."""
+        if self.vae_dir is None:
+            want = os.path.join(self.params.pretrained_pipe_path or "<pretrained_pipe_path>", "vae")
+            raise NotImplementedError(f"VAE encoding needs the AutoencoderKL in {want!r} (config.json + safetensors); without "
+                                      "it, train from cached-feature shards")
+        if self.vae_encoder is None:
+            self.vae_encoder = load_vae_encoder(self.vae_dir, device=self.accelerator.device)
+        return self.vae_encoder.encode(images, apply_shift=False)
 
     def extract_embeddings(self, captions):
         raise NotImplementedError("text encoding is outside the hot-path scope; train from cached-feature shards")

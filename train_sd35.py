@@ -6,10 +6,11 @@ driving the MI355X-native MMDiT path (BASELINE config 4).
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train_sd35.py --config config.yaml
 
 ``pretrained_model_path`` (or ``pretrained_pipe_path``/transformer) must be a LOCAL diffusers directory; with neither the
-SD3.5-Medium architecture is random-initialised (no network here).  The three text encoders and the VAE encoder are outside
-the hot-path scope: training consumes cached-feature shards whose samples carry the prompt embeddings (``emb.pt`` [333,
-4096]) and the pooled projection (``pooled.pt`` [2048]); validation decodes its latents on the HIP AutoencoderKL decoder
-(yat_amd/autoencoder_kl.py) when ``<pretrained_pipe_path>/vae`` holds the VAE.
+SD3.5-Medium architecture is random-initialised (no network here).  The three text encoders are outside the hot-path
+scope: training consumes cached-feature shards whose samples carry the prompt embeddings (``emb.pt`` [333, 4096]) and the
+pooled projection (``pooled.pt`` [2048]); ``python -m yat_amd.extract_latents`` makes their latents on the HIP AutoencoderKL
+encoder (yat_amd/autoencoder_kl_encoder.py), which ``extract_latents`` also uses; validation decodes its latents on the HIP
+AutoencoderKL decoder (yat_amd/autoencoder_kl.py) when ``<pretrained_pipe_path>/vae`` holds the VAE.
 
 Reference quirks: ``SD35Trainer.optimize(self, model, batch)`` (:165) has a pre-refactor signature with a
 ``(latents, embeddings, pooled_projections)`` batch no sampler produces any more, while ``Model.run`` calls
@@ -26,7 +27,7 @@ import torch
 
 from yat_amd.common.training_parameters_reader import TrainingParameters
 from yat_amd.common.trainer import Model
-from yat_amd.autoencoder_kl import decode_validation, load_vae_decoder
+from yat_amd.autoencoder_kl import decode_validation, load_vae_decoder, load_vae_encoder
 from yat_amd.common.aspect_ratios import ASPECT_RATIO_1024_BIN
 from yat_amd.recipe import SD3Recipe
 from yat_amd.scheduler import FlowMatchSchedule
@@ -55,11 +56,23 @@ class SD35Trainer(Model):
         self.aspect_ratios = ASPECT_RATIO_1024_BIN                                              # :55
         self.recipe = SD3Recipe(self.model, self.scheduler, device=dev)
         self.pipe = None
-        self.vae_dir = find_vae_dir(params.pretrained_pipe_path)                              # decoder only
+        self.vae_dir = find_vae_dir(params.pretrained_pipe_path)
         self.vae = None                                                                        # built at the first validate()
+        self.vae_encoder = None                                                                # built at the first extract_latents()
 
     def extract_latents(self, images):
-        raise NotImplementedError("VAE encoding is outside the hot-path scope; train from cached-feature shards")
+        """train_sd35.py:63-77 on the HIP AutoencoderKL encoder (yat_amd/autoencoder_kl_encoder.py), built from
+        ``<pretrained_pipe_path>/vae`` at the first call: ``(vae.encode(images).latent_dist.sample() - shift_factor) *
+        scaling_factor``; the sample's noise comes from the device's global generator, as there.  The reference passes the
+        images through ``image_processor.preprocess`` first (:68); for the fetcher's [-1, 1] tensors at bucket sizes that is
+        taken to be the identity and is not restated here."""
+        if self.vae_dir is None:
+            want = os.path.join(self.params.pretrained_pipe_path or "<pretrained_pipe_path>", "vae")
+            raise NotImplementedError(f"VAE encoding needs the AutoencoderKL in {want!r} (config.json + safetensors); without "
+                                      "it, train from cached-feature shards")
+        if self.vae_encoder is None:
+            self.vae_encoder = load_vae_encoder(self.vae_dir, device=self.accelerator.device)
+        return self.vae_encoder.encode(images, apply_shift=True)
 
     def extract_embeddings(self, captions):
         raise NotImplementedError("text encoding is outside the hot-path scope; train from cached-feature shards")

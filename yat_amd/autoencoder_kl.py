@@ -1,4 +1,5 @@
-"""AutoencoderKL decoder on the HIP path: the VAE decode of the PixArt-Sigma and SD3.5 validation images
+"""AutoencoderKL decoder on the HIP path (and what the encoder, yat_amd/autoencoder_kl_encoder.py, shares with it: the
+ResnetBlock2D / Attention key tables, packing and launches): the VAE decode of the PixArt-Sigma and SD3.5 validation images
 (train_pixart_sigma.py:137-144, train_sd35.py:150-156), ``vae.decode(latent / vae.config.scaling_factor)`` ->
 ``image_processor.postprocess``, with the VAE in bf16.
 
@@ -96,7 +97,9 @@ def parse_config(raw: dict) -> KLDecoderConfig:
     return cfg
 
 
-def _validate(cfg: KLDecoderConfig) -> None:
+def validate_widths(cfg) -> None:
+    """The checks both halves share (the encoder's configuration has the same fields): GroupNorm groups, conv / GEMM
+    widths, the mid-block attention width."""
     g = cfg.norm_num_groups
     for c in cfg.block_out_channels:
         if g <= 0 or c % g:
@@ -106,21 +109,34 @@ def _validate(cfg: KLDecoderConfig) -> None:
     mid = cfg.block_out_channels[-1]
     if cfg.mid_block_add_attention and mid not in ATTN_DIMS:
         raise NotImplementedError(f"mid-block width {mid}: the single-head attention is built for {ATTN_DIMS}")
-    if cfg.out_channels != 3:
-        raise NotImplementedError(f"out_channels {cfg.out_channels} (built: 3)")
     if cfg.layers_per_block <= 0:
         raise NotImplementedError(f"layers_per_block {cfg.layers_per_block}")
     if cfg.latent_channels <= 0:
         raise ValueError(f"latent_channels {cfg.latent_channels}")
 
 
-def _resnet_keys(p, cin, cout):
+def _validate(cfg: KLDecoderConfig) -> None:
+    validate_widths(cfg)
+    if cfg.out_channels != 3:
+        raise NotImplementedError(f"out_channels {cfg.out_channels} (built: 3)")
+
+
+def resnet_keys(p, cin, cout):
+    """ResnetBlock2D under the prefix ``p`` -> {key: shape}."""
     k = {p + "norm1.weight": (cin,), p + "norm1.bias": (cin,), p + "conv1.weight": (cout, cin, 3, 3), p + "conv1.bias": (cout,),
          p + "norm2.weight": (cout,), p + "norm2.bias": (cout,), p + "conv2.weight": (cout, cout, 3, 3),
          p + "conv2.bias": (cout,)}
     if cin != cout:
         k.update({p + "conv_shortcut.weight": (cout, cin, 1, 1), p + "conv_shortcut.bias": (cout,)})
     return k
+
+
+def attention_keys(a, c):
+    """The mid-block Attention of width ``c`` under the prefix ``a`` (current names) -> {key: shape}."""
+    keys = {a + "group_norm.weight": (c,), a + "group_norm.bias": (c,)}
+    for t in ("to_q", "to_k", "to_v", "to_out.0"):
+        keys.update({a + t + ".weight": (c, c), a + t + ".bias": (c,)})
+    return keys
 
 
 def _resnets(cfg: KLDecoderConfig):
@@ -149,12 +165,9 @@ def expected_keys(cfg: KLDecoderConfig) -> dict:
     keys.update({"decoder.conv_in.weight": (ch[-1], lat, 3, 3), "decoder.conv_in.bias": (ch[-1],)})
     res, ups = _resnets(cfg)
     for p, cin, cout in res:
-        keys.update(_resnet_keys(p, cin, cout))
+        keys.update(resnet_keys(p, cin, cout))
     if cfg.mid_block_add_attention:
-        a, c = "decoder.mid_block.attentions.0.", ch[-1]
-        keys.update({a + "group_norm.weight": (c,), a + "group_norm.bias": (c,)})
-        for t in ("to_q", "to_k", "to_v", "to_out.0"):
-            keys.update({a + t + ".weight": (c, c), a + t + ".bias": (c,)})
+        keys.update(attention_keys("decoder.mid_block.attentions.0.", ch[-1]))
     for p, c in ups:
         keys.update({p + "weight": (c, c, 3, 3), p + "bias": (c,)})
     keys.update({"decoder.conv_norm_out.weight": (ch[0],), "decoder.conv_norm_out.bias": (ch[0],),
@@ -166,13 +179,13 @@ def _ours(k: str) -> bool:
     return k.startswith("decoder.") or k.startswith("post_quant_conv.")
 
 
-def convert_deprecated(sd: dict) -> dict:
-    """Old diffusers checkpoints name the mid-block attention ``query`` / ``key`` / ``value`` / ``proj_attn``, sometimes as
-    1x1-conv tensors [C, C, 1, 1]: renamed to ``to_q`` / ``to_k`` / ``to_v`` / ``to_out.0`` with Linear shapes.  Other keys
-    pass through unchanged."""
+def convert_deprecated(sd: dict, half: str = "decoder") -> dict:
+    """Old diffusers checkpoints name the mid-block attention of ``half`` ('decoder' / 'encoder') ``query`` / ``key`` /
+    ``value`` / ``proj_attn``, sometimes as 1x1-conv tensors [C, C, 1, 1]: renamed to ``to_q`` / ``to_k`` / ``to_v`` /
+    ``to_out.0`` with Linear shapes.  Other keys pass through unchanged."""
     out = {}
     for k, v in sd.items():
-        if k.startswith("decoder.mid_block.attentions."):
+        if k.startswith(half + ".mid_block.attentions."):
             head, _, leaf = k.rpartition(".")                  # e.g. (decoder.mid_block.attentions.0.query, weight)
             base, _, name = head.rpartition(".")
             if name in DEPRECATED_ATTN:
@@ -201,6 +214,26 @@ def pad_latent_channels(t: torch.Tensor, n: int, dim: int) -> torch.Tensor:
     return torch.cat([t, t.new_zeros(shape)], dim)
 
 
+def pack_resnet(b: dict, p: str, q: str, cin: int, cout: int) -> dict:
+    """ResnetBlock2D ``p`` of the bf16 state dict ``b`` -> its packed weights under the prefix ``q``."""
+    out = {q + "norm1.w": b[p + "norm1.weight"], q + "norm1.b": b[p + "norm1.bias"],
+           q + "conv1.w": pack_conv3x3(b[p + "conv1.weight"]), q + "conv1.b": b[p + "conv1.bias"],
+           q + "norm2.w": b[p + "norm2.weight"], q + "norm2.b": b[p + "norm2.bias"],
+           q + "conv2.w": pack_conv3x3(b[p + "conv2.weight"]), q + "conv2.b": b[p + "conv2.bias"]}
+    if cin != cout:
+        out[q + "sc.w"] = b[p + "conv_shortcut.weight"].reshape(cout, cin).contiguous()
+        out[q + "sc.b"] = b[p + "conv_shortcut.bias"]
+    return out
+
+
+def pack_attention(b: dict, a: str) -> dict:
+    """The mid-block Attention ``a`` of the bf16 state dict ``b`` -> ``attn.*``: to_q | to_k | to_v fused."""
+    return {"attn.gn.w": b[a + "group_norm.weight"], "attn.gn.b": b[a + "group_norm.bias"],
+            "attn.qkv.w": torch.cat([b[a + t + ".weight"] for t in ("to_q", "to_k", "to_v")], 0).contiguous(),
+            "attn.qkv.b": torch.cat([b[a + t + ".bias"] for t in ("to_q", "to_k", "to_v")], 0).contiguous(),
+            "attn.out.w": b[a + "to_out.0.weight"].contiguous(), "attn.out.b": b[a + "to_out.0.bias"]}
+
+
 def pack_weights(cfg: KLDecoderConfig, sd: dict) -> dict:
     """Deprecated-name conversion, strict check and the one-time re-pack on the host, in bf16: 3x3 convs to [Cout, 3, 3, Cin],
     1x1 convs and Linears to [N, K], to_q | to_k | to_v fused, the latent channels padded to a multiple of 8."""
@@ -217,20 +250,9 @@ def pack_weights(cfg: KLDecoderConfig, sd: dict) -> dict:
     out["conv_in.b"] = b["decoder.conv_in.bias"]
     res, ups = _resnets(cfg)
     for p, cin, cout in res:
-        q = p[len("decoder."):]
-        out.update({q + "norm1.w": b[p + "norm1.weight"], q + "norm1.b": b[p + "norm1.bias"],
-                    q + "conv1.w": pack_conv3x3(b[p + "conv1.weight"]), q + "conv1.b": b[p + "conv1.bias"],
-                    q + "norm2.w": b[p + "norm2.weight"], q + "norm2.b": b[p + "norm2.bias"],
-                    q + "conv2.w": pack_conv3x3(b[p + "conv2.weight"]), q + "conv2.b": b[p + "conv2.bias"]})
-        if cin != cout:
-            out[q + "sc.w"] = b[p + "conv_shortcut.weight"].reshape(cout, cin).contiguous()
-            out[q + "sc.b"] = b[p + "conv_shortcut.bias"]
+        out.update(pack_resnet(b, p, p[len("decoder."):], cin, cout))
     if cfg.mid_block_add_attention:
-        a = "decoder.mid_block.attentions.0."
-        out.update({"attn.gn.w": b[a + "group_norm.weight"], "attn.gn.b": b[a + "group_norm.bias"],
-                    "attn.qkv.w": torch.cat([b[a + t + ".weight"] for t in ("to_q", "to_k", "to_v")], 0).contiguous(),
-                    "attn.qkv.b": torch.cat([b[a + t + ".bias"] for t in ("to_q", "to_k", "to_v")], 0).contiguous(),
-                    "attn.out.w": b[a + "to_out.0.weight"].contiguous(), "attn.out.b": b[a + "to_out.0.bias"]})
+        out.update(pack_attention(b, "decoder.mid_block.attentions.0."))
     for p, c in ups:
         q = p[len("decoder."):]
         out[q + "w"] = pack_conv3x3(b[p + "weight"])
@@ -245,31 +267,10 @@ def load_vae_dir(vae_dir: str):
     return parse_config(read_config(vae_dir)), load_tensors(vae_dir, _ours)
 
 
-class AutoencoderKLDecoderHIP(VAEHalfHIP):
-    """The decoder half of AutoencoderKL in bf16 on the HIP kernels.  ``decode`` runs one image at a time on the current
-    stream through activation buffers sized for the largest stage (kept between calls of the same latent size)."""
-    load_vae_dir = staticmethod(load_vae_dir)
-    pack_weights = staticmethod(pack_weights)
+class KLBlocksHIP(VAEHalfHIP):
+    """What both AutoencoderKL halves run on (yat_amd/autoencoder_kl_encoder.py is the other): GroupNorm, ResnetBlock2D and
+    the mid-block Attention over the packed weights ``self.w`` and the buffers ``t`` / ``u`` / ``ws`` of ``_alloc_buffers``."""
 
-    def _alloc_buffers(self, h, w):
-        from . import ops
-        cfg, ch = self.cfg, self.cfg.block_out_channels
-        rev = list(reversed(ch))
-        # the largest activation: a block's widest input or output at its resolution, or its upsampled output
-        act, hh, ww = h * w * max(ch[-1], cfg.latent_padded), h, w
-        for i, c in enumerate(rev):
-            prev = rev[i - 1] if i else rev[0]
-            act = max(act, hh * ww * max(prev, c))
-            if i < len(rev) - 1:
-                hh, ww = 2 * hh, 2 * ww
-                act = max(act, hh * ww * c)
-        ws = max(ops.vae_groupnorm_workspace_bytes(1, hh * ww, ch[0], cfg.norm_num_groups),
-                 ops.vae_groupnorm_workspace_bytes(1, h * w, ch[-1], cfg.norm_num_groups))
-        e = lambda k: torch.empty(max(k, 8), dtype=BF16, device=self.device)  # noqa: E731
-        return {"xa": e(act), "xb": e(act), "t": e(act), "u": e(max(act, 3 * h * w * ch[-1])),
-                "z": e(h * w * cfg.latent_padded), "ws": torch.empty(max(ws, 16), dtype=torch.uint8, device=self.device)}
-
-    # ------------------------------------------------------------------------------------------------ blocks
     def _gn(self, x, y, npx, c, key, silu, bf):
         from . import ops
         ops.vae_groupnorm(x, self.w[key + ".w"], self.w[key + ".b"], y, 1, npx, c, self.cfg.norm_num_groups, bf["ws"], EPS,
@@ -302,6 +303,31 @@ class AutoencoderKLDecoderHIP(VAEHalfHIP):
         ops.vae_attn_fwd(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], t, 1, npx, c, 3 * c, c)
         ops.gemm(t, self.w["attn.out.w"], out[:npx * c].view(npx, c), M=npx, N=c, K=c, bias=self.w["attn.out.b"],
                  residual=x.view(npx, c))
+
+
+class AutoencoderKLDecoderHIP(KLBlocksHIP):
+    """The decoder half of AutoencoderKL in bf16 on the HIP kernels.  ``decode`` runs one image at a time on the current
+    stream through activation buffers sized for the largest stage (kept between calls of the same latent size)."""
+    load_vae_dir = staticmethod(load_vae_dir)
+    pack_weights = staticmethod(pack_weights)
+
+    def _alloc_buffers(self, h, w):
+        from . import ops
+        cfg, ch = self.cfg, self.cfg.block_out_channels
+        rev = list(reversed(ch))
+        # the largest activation: a block's widest input or output at its resolution, or its upsampled output
+        act, hh, ww = h * w * max(ch[-1], cfg.latent_padded), h, w
+        for i, c in enumerate(rev):
+            prev = rev[i - 1] if i else rev[0]
+            act = max(act, hh * ww * max(prev, c))
+            if i < len(rev) - 1:
+                hh, ww = 2 * hh, 2 * ww
+                act = max(act, hh * ww * c)
+        ws = max(ops.vae_groupnorm_workspace_bytes(1, hh * ww, ch[0], cfg.norm_num_groups),
+                 ops.vae_groupnorm_workspace_bytes(1, h * w, ch[-1], cfg.norm_num_groups))
+        e = lambda k: torch.empty(max(k, 8), dtype=BF16, device=self.device)  # noqa: E731
+        return {"xa": e(act), "xb": e(act), "t": e(act), "u": e(max(act, 3 * h * w * ch[-1])),
+                "z": e(h * w * cfg.latent_padded), "ws": torch.empty(max(ws, 16), dtype=torch.uint8, device=self.device)}
 
     def _decode_one(self, z, out, h, w):
         from . import ops
@@ -381,6 +407,15 @@ def vae_class(raw: dict) -> str:
     if "block_out_channels" in raw or "up_block_types" in raw:
         return "AutoencoderKL"
     raise NotImplementedError("vae/config.json names no VAE class and has neither AutoencoderKL nor AutoencoderDC keys")
+
+
+def load_vae_encoder(vae_dir: str, device="cuda"):
+    """The HIP encoder for the VAE in ``vae_dir``, picked by ``vae_class``."""
+    if vae_class(read_config(vae_dir)) == "AutoencoderDC":
+        from .dcae_encoder import AutoencoderDCEncoderHIP
+        return AutoencoderDCEncoderHIP.from_pretrained(vae_dir, device=device)
+    from .autoencoder_kl_encoder import AutoencoderKLEncoderHIP
+    return AutoencoderKLEncoderHIP.from_pretrained(vae_dir, device=device)
 
 
 def load_vae_decoder(vae_dir: str, device="cuda"):

@@ -119,6 +119,8 @@ SIGNATURES = {
     "yat_vae_groupnorm_workspace_bytes": (U64, [I, I, I, I]),
     "yat_vae_groupnorm": (I, [I, I, I, I, F, P, P, P, I, P, P, P]),
     "yat_vae_attn_fwd": (I, [I, I, I, P, P, P, I, P, I, P]),
+    "yat_vae_conv3x3_down": (I, [I, I, I, I, I, P, P, P, P, P]),
+    "yat_vae_kl_sample": (I, [I, I, I, I, P, P, I, F, F, P, P]),
     "yat_plan_op_id": (I, [C.c_char_p]),
     "yat_plan_replay": (I, [C.POINTER(PlanEntry), I, C.POINTER(I)]),
     "yat_comm_available": (I, []),

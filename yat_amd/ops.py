@@ -899,3 +899,23 @@ def vae_attn_fwd(q, k, v, out, B, N, dh, ld, ldo=None):
                                  _stream())
     _l.check(rc, "yat_vae_attn_fwd")
     return out
+
+
+# ------------------------------------------------------------------------- AutoencoderKL encoder (yat_amd/autoencoder_kl_encoder.py)
+def vae_conv3x3_down(x, w, y, B, H, W, Cin, Cout, bias=None):
+    """Downsample2D of DownEncoderBlock2D: F.pad(x, (0, 1, 0, 1)) -> 3x3 conv, stride 2, no padding, NHWC
+    (include/yat_hip.h yat_vae_conv3x3_down); x [B, H, W, Cin] -> y [B, H/2, W/2, Cout]; w is [Cout, 3, 3, Cin]."""
+    _chk_bf16(x, w, y, bias)
+    rc = _lib().yat_vae_conv3x3_down(B, H, W, Cin, Cout, _p(x), _p(w), _p(bias), _p(y), _stream())
+    _l.check(rc, "yat_vae_conv3x3_down")
+    return y
+
+
+def vae_kl_sample(moments, noise, out, B, HW, L, ld, scale, shift=None):
+    """DiagonalGaussianDistribution.sample() (``noise`` [B, L, HW]) or .mode() (``noise`` None) of NHWC ``moments`` [B, HW, ld],
+    then ``- shift`` (when given) and ``* scale`` -> ``out`` [B, L, HW] (include/yat_hip.h yat_vae_kl_sample)."""
+    _chk_bf16(moments, noise, out)
+    rc = _lib().yat_vae_kl_sample(B, HW, L, int(ld), _p(moments), _p(noise), int(shift is not None),
+                                  float(shift if shift is not None else 0.0), float(scale), _p(out), _stream())
+    _l.check(rc, "yat_vae_kl_sample")
+    return out

@@ -1,6 +1,6 @@
-"""What the VAE halves on the HIP path share (yat_amd/dcae.py, yat_amd/dcae_encoder.py, yat_amd/autoencoder_kl.py): reading
-a diffusers ``vae`` directory, the strict state-dict check, the host side of a ``*HIP`` class, the uint8 postprocess, the
-trainers' validation-image loop and the latents -> PNG command line."""
+"""What the VAE halves on the HIP path share (yat_amd/dcae.py, yat_amd/dcae_encoder.py, yat_amd/autoencoder_kl.py,
+yat_amd/autoencoder_kl_encoder.py): reading a diffusers ``vae`` directory, the strict state-dict check, the host side of a
+``*HIP`` class, the uint8 postprocess, the trainers' validation-image loop and the latents -> PNG command line."""
 from __future__ import annotations
 
 import argparse
