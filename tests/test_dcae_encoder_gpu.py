@@ -84,6 +84,52 @@ def test_conv3x3_down_shortcut_alone_is_exact():
         assert torch.equal(y.cpu().permute(0, 3, 1, 2), want)
 
 
+# ------------------------------------------------------------------------------------------------------- tap placement
+def _tap_conv(kind, x, w, B, H, W, C):
+    """One launch of the entry point ``kind`` on NCHW ``x`` [B, C, H, W], no bias, no shortcut -> (S, P, upsampled, NCHW y)."""
+    from yat_amd import ops
+    S, up = (2, False) if kind == "down" else (1, kind == "up")
+    Ho, Wo = (2 * H, 2 * W) if up else (H // S, W // S)
+    xd, wd = x.permute(0, 2, 3, 1).contiguous().to(DEV), w.permute(0, 2, 3, 1).contiguous().to(DEV)
+    y = torch.full((B, Ho, Wo, C), float("nan"), dtype=BF, device=DEV)
+    if kind in ("plain", "up"):
+        ops.dcae_conv3x3(xd, wd, y, B, Ho, Wo, C, C, upsample=up)
+    elif kind == "down":
+        ops.dcae_conv3x3_down(xd, wd, y, B, H, W, C, C, bias=None, shortcut=False)
+    else:
+        ops.dcae_conv3x3_mean(xd, wd, y, B, H, W, C, C, bias=None, shortcut=False)
+    torch.cuda.synchronize()
+    return S, 1, up, y.cpu().permute(0, 3, 1, 2)
+
+
+@pytest.mark.parametrize("tap", [(0, 0), (2, 2)])
+@pytest.mark.parametrize("C", [64, 40])                       # Cin % 64 == 0: one tap per K-tile; 40: taps change inside one
+@pytest.mark.parametrize("kind", ["plain", "up", "down", "mean"])
+def test_conv3x3_tap_placement_is_exact(kind, C, tap):
+    """Identity channel map on one tap, zero elsewhere, no bias: the output is the input pixel that tap reads,
+    (S oy + ty - P, S ox + tx - P) of the (nearest-upsampled) input, bit for bit, and exact zeros where that lies outside.
+    The (S, P) = (2, 0) geometry is pinned the same way by test_vae_kl_encoder_gpu.test_conv3x3_down_tap_placement_is_exact."""
+    B = 2
+    H, W = (6, 10) if kind == "up" else (12, 20)              # 12 x 20 on the output side (stride 1) / the input side (stride 2)
+    ty, tx = tap
+    x = _asymmetric(B, C, H, W, torch.Generator().manual_seed(C + ty))
+    w = torch.zeros(C, C, 3, 3, dtype=BF)
+    w[torch.arange(C), torch.arange(C), ty, tx] = 1.0
+    S, P, up, y = _tap_conv(kind, x, w, B, H, W, C)
+    src = x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3) if up else x          # nearest x2
+    Ho, Wo = src.shape[2] // S, src.shape[3] // S
+    assert y.shape == (B, C, Ho, Wo)
+    want = F.pad(src, (P, P, P, P))[:, :, ty:ty + S * Ho:S, tx:tx + S * Wo:S]
+    assert torch.equal(y, want)
+    # the border that tap reads from outside the image: exact zeros
+    if tap == (0, 0):
+        assert not y[:, :, 0, :].any() and not y[:, :, :, 0].any()
+    elif S == 1:
+        assert not y[:, :, -1, :].any() and not y[:, :, :, -1].any()
+    else:
+        assert torch.equal(y, src[:, :, 1::2, 1::2])          # stride 2, pad 1, tap (2, 2): wholly inside the image
+
+
 # -------------------------------------------------------------------------------------------------------- conv3x3_mean
 @pytest.mark.parametrize("B,Cin,Cout,H,W,sc", [(1, 1024, 32, 8, 10, True), (2, 64, 8, 13, 11, True),
                                                (1, 1024, 32, 32, 32, True), (1, 64, 8, 9, 7, False)])

@@ -14,171 +14,85 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------------------------- conv3x3
-// The tile, its B operand, fragment reads and K loop are dcae_conv.hpp (shared with the encoder convs, dcae_enc.hip); this
-// file adds the decoder's A-operand address math (optional nearest x2 upsample) and its epilogue.
-struct ConvP {
-    const bf16_t* x;      // [B, Hin, Win, Cin]
-    const bf16_t* w;      // [Cout, 9 * Cin]
+// The kernel is dcae_conv.hpp's (stride 1, pad 1, with or without the nearest x2 upsample of the input); this file adds the
+// decoder's epilogue and the direct kernel for Cout <= 4.
+//
+// epilogue of 4 consecutive output channels n..n+3 of pixel m:
+// +bias -> bf16 -> [SiLU -> bf16] -> [+ shortcut -> bf16] -> [+ residual -> bf16]
+struct conv_epilogue {
     const bf16_t* bias;   // [Cout] or null
     const bf16_t* sc;     // shortcut source or null
     const bf16_t* res;    // [B, H, W, Cout] or null
     bf16_t* y;            // [B, H, W, Cout] (NCHW for the direct kernel when nchw)
-    int B, H, W, Cin, Cout, Hin, Win, up, silu, sc_mode, sc_ch, sc_rep, nchw;
-    int M, K, nbm, nbn;
-    uint64_t x_bytes, w_bytes;
+    int silu, sc_mode, sc_ch, sc_rep;
+
+    __device__ __forceinline__ void operator()(const ConvGeom& g, float (&v)[4], int m, int n) const {
+        if (bias) {
+            float bb[4];
+            unpack4(*reinterpret_cast<const u32x2*>(bias + n), bb);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] += bb[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = rbf(v[e]);
+        if (silu) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = rbf(silu_f(v[e]));
+        }
+        if (sc_mode == 1) {                    // repeat_interleave(z, rep, dim=C): channel c adds z[c // rep]
+            const bf16_t* s = sc + (int64_t)m * sc_ch;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = rbf(v[e] + bf2f(s[(n + e) / sc_rep]));
+        } else if (sc_mode == 2) {             // pixel_shuffle(repeat_interleave(x, rep), 2) from the half-resolution input
+            int b, oy, ox;
+            conv_pixel(g, m, b, oy, ox);
+            const bf16_t* s = sc + (((int64_t)b * (g.Ho >> 1) + (oy >> 1)) * (g.Wo >> 1) + (ox >> 1)) * sc_ch;
+            const int sub = 2 * (oy & 1) + (ox & 1);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = rbf(v[e] + bf2f(s[(4 * (n + e) + sub) / sc_rep]));
+        }
+        if (res) {
+            float r[4];
+            unpack4(*reinterpret_cast<const u32x2*>(res + (int64_t)m * g.Cout + n), r);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = rbf(v[e] + r[e]);
+        }
+        *reinterpret_cast<u32x2*>(y + (int64_t)m * g.Cout + n) = pack4(v[0], v[1], v[2], v[3]);
+    }
 };
-
-template <bool TAPU>
-__device__ __forceinline__ void conv_stage_a(const ConvP& p, __amdgpu_buffer_rsrc_t rx, char* lds, int k0, int wave,
-                                             const int (&rb)[4], const int (&ry)[4], const int (&rxx)[4], const int (&cc)[4]) {
-    int tapu = 0, ciu = 0;
-    if (TAPU) {                                        // Cin % 64 == 0: the whole K-tile lies in one tap
-        tapu = k0 / p.Cin;
-        ciu = k0 - tapu * p.Cin;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int piece = j * 4 + wave;
-        const int kg = k0 + cc[j] * 8;
-        int tap, ci;
-        if (TAPU) {
-            tap = tapu;
-            ci = ciu + cc[j] * 8;
-        } else {
-            tap = kg / p.Cin;
-            ci = kg - tap * p.Cin;
-        }
-        const int t3 = tap / 3;
-        int iy = ry[j] + t3 - 1, ix = rxx[j] + (tap - 3 * t3) - 1;
-        const bool ok = kg < p.K && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-        if (p.up) {
-            iy >>= 1;
-            ix >>= 1;
-        }
-        const uint32_t voff = ok ? (uint32_t)((((int64_t)(rb[j] + iy) * p.Win + ix) * p.Cin + ci) * 2) : YAT_OOB;
-        lds_dma16(rx, (YAT_LDS void*)(lds + piece * 1024), voff);
-    }
-}
-
-// epilogue of 4 consecutive output channels n..n+3 of pixel m:
-// +bias -> bf16 -> [SiLU -> bf16] -> [+ shortcut -> bf16] -> [+ residual -> bf16]
-__device__ __forceinline__ void conv_epilogue(const ConvP& p, float (&v)[4], int m, int n) {
-    if (p.bias) {
-        float bb[4];
-        unpack4(*reinterpret_cast<const u32x2*>(p.bias + n), bb);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += bb[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = rbf(v[e]);
-    if (p.silu) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = rbf(silu_f(v[e]));
-    }
-    if (p.sc_mode == 1) {                    // repeat_interleave(z, rep, dim=C): channel c adds z[c // rep]
-        const bf16_t* s = p.sc + (int64_t)m * p.sc_ch;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = rbf(v[e] + bf2f(s[(n + e) / p.sc_rep]));
-    } else if (p.sc_mode == 2) {             // pixel_shuffle(repeat_interleave(x, rep), 2) from the half-resolution input
-        const int hw = p.H * p.W, b = m / hw, pix = m - b * hw, oy = pix / p.W, ox = pix - oy * p.W;
-        const bf16_t* s = p.sc + (((int64_t)b * (p.H >> 1) + (oy >> 1)) * (p.W >> 1) + (ox >> 1)) * p.sc_ch;
-        const int sub = 2 * (oy & 1) + (ox & 1);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = rbf(v[e] + bf2f(s[(4 * (n + e) + sub) / p.sc_rep]));
-    }
-    if (p.res) {
-        float r[4];
-        unpack4(*reinterpret_cast<const u32x2*>(p.res + (int64_t)m * p.Cout + n), r);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = rbf(v[e] + r[e]);
-    }
-    *reinterpret_cast<u32x2*>(p.y + (int64_t)m * p.Cout + n) = pack4(v[0], v[1], v[2], v[3]);
-}
-
-template <bool TAPU>
-__global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(ConvP p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-
-    int m0, n0;
-    conv_tile_origin(p.nbm, p.nbn, m0, n0);
-
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, p.x_bytes);
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.w, p.w_bytes);
-
-    // this lane's four A rows (output pixels) and the source chunk each of its LDS slots holds
-    int rb[4], ry[4], rxx[4], cc[4];
-    const int hw = p.H * p.W;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int r = (j * 4 + wave) * 8 + (lane >> 3);
-        const int m = m0 + r;
-        cc[j] = swz128(r, lane & 7);
-        if (m < p.M) {
-            const int b = m / hw, pix = m - b * hw, oy = pix / p.W;
-            rb[j] = b * p.Hin;
-            ry[j] = oy;
-            rxx[j] = pix - oy * p.W;
-        } else {
-            rb[j] = 0;
-            ry[j] = -4;                                  // every tap out of range -> zeros
-            rxx[j] = 0;
-        }
-    }
-
-    f32x4 acc[4][4];
-    conv_mainloop(smem, rw, p.Cout, p.K, n0, wave, lane, acc,
-                  [&](char* lds, int k0) { conv_stage_a<TAPU>(p, rx, lds, k0, wave, rb, ry, rxx, cc); });
-
-    // lane owns pixel m = .. + (lane & 15) and output channels n = .. + 4 (lane >> 4) + 0..3
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m0 + wm * 64 + i * 16 + (lane & 15);
-        if (m >= p.M) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wn * 64 + j * 16 + 4 * (lane >> 4);
-            if (n >= p.Cout) continue;
-            float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-            conv_epilogue(p, v, m, n);
-        }
-    }
-}
 
 // Cout <= 4 (Decoder.conv_out, C0 -> RGB): one output pixel per thread, all Cout channels, the weights broadcast from
 // LDS.  The input is read once per tap in 16-B chunks (neighbouring threads share rows through L1 / L2) instead of being
 // staged into a 128-wide MFMA tile of which 3 columns would be used.
 constexpr int SMALL_COUT = 4;
 
-__global__ __launch_bounds__(256) void conv3x3_small_kernel(ConvP p) {
+__global__ __launch_bounds__(256) void conv3x3_small_kernel(ConvGeom g, conv_epilogue e, int nchw) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16_t* wl = reinterpret_cast<bf16_t*>(smem);
-    const int nw = p.Cout * p.K;                               // multiple of 8 (Cin % 8 == 0)
+    const int nw = g.Cout * g.K;                               // multiple of 8 (Cin % 8 == 0)
     for (int i = threadIdx.x * 8; i < nw; i += 256 * 8)
-        *reinterpret_cast<u32x4*>(wl + i) = *reinterpret_cast<const u32x4*>(p.w + i);
+        *reinterpret_cast<u32x4*>(wl + i) = *reinterpret_cast<const u32x4*>(g.w + i);
     __syncthreads();
     const int m = blockIdx.x * 256 + threadIdx.x;
-    if (m >= p.M) return;
-    const int hw = p.H * p.W, b = m / hw, pix = m - b * hw, oy = pix / p.W, ox = pix - oy * p.W;
+    if (m >= g.M) return;
+    const int hw = g.Ho * g.Wo, b = m / hw, pix = m - b * hw, oy = pix / g.Wo, ox = pix - oy * g.Wo;
     float acc[SMALL_COUT] = {0.f, 0.f, 0.f, 0.f};
     for (int tap = 0; tap < 9; ++tap) {
         int iy = oy + tap / 3 - 1, ix = ox + tap % 3 - 1;
-        if ((unsigned)iy >= (unsigned)p.H || (unsigned)ix >= (unsigned)p.W) continue;
-        if (p.up) {
+        if ((unsigned)iy >= (unsigned)g.Ho || (unsigned)ix >= (unsigned)g.Wo) continue;
+        if (g.up) {
             iy >>= 1;
             ix >>= 1;
         }
-        const bf16_t* xp = p.x + (((int64_t)b * p.Hin + iy) * p.Win + ix) * p.Cin;
-        for (int c = 0; c < p.Cin; c += 8) {
+        const bf16_t* xp = g.x + (((int64_t)b * g.H + iy) * g.W + ix) * g.Cin;
+        for (int c = 0; c < g.Cin; c += 8) {
             float xv[8];
             unpack8(*reinterpret_cast<const u32x4*>(xp + c), xv);
 #pragma unroll
             for (int co = 0; co < SMALL_COUT; ++co) {
-                if (co < p.Cout) {
+                if (co < g.Cout) {
                     float wv[8];
-                    unpack8(*reinterpret_cast<const u32x4*>(wl + co * p.K + tap * p.Cin + c), wv);
+                    unpack8(*reinterpret_cast<const u32x4*>(wl + co * g.K + tap * g.Cin + c), wv);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) acc[co] = __builtin_fmaf(xv[e], wv[e], acc[co]);
                 }
@@ -187,14 +101,14 @@ __global__ __launch_bounds__(256) void conv3x3_small_kernel(ConvP p) {
     }
 #pragma unroll
     for (int co = 0; co < SMALL_COUT; ++co) {
-        if (co >= p.Cout) break;
+        if (co >= g.Cout) break;
         float v = acc[co];
-        if (p.bias) v += bf2f(p.bias[co]);
+        if (e.bias) v += bf2f(e.bias[co]);
         v = rbf(v);
-        if (p.silu) v = rbf(silu_f(v));
-        if (p.res) v = rbf(v + bf2f(p.res[(int64_t)m * p.Cout + co]));
-        const int64_t o = p.nchw ? ((int64_t)b * p.Cout + co) * hw + pix : (int64_t)m * p.Cout + co;
-        p.y[o] = f2bf(v);
+        if (e.silu) v = rbf(silu_f(v));
+        if (e.res) v = rbf(v + bf2f(e.res[(int64_t)m * g.Cout + co]));
+        const int64_t o = nchw ? ((int64_t)b * g.Cout + co) * hw + pix : (int64_t)m * g.Cout + co;
+        e.y[o] = f2bf(v);
     }
 }
 
@@ -310,51 +224,36 @@ extern "C" {
 int yat_dcae_conv3x3(int B, int H, int W, int Cin, int Cout, int upsample, int silu, const void* x, const void* w,
                      const void* bias, int shortcut_mode, const void* shortcut, int shortcut_channels, const void* residual,
                      int out_nchw, void* y, yat_stream_t stream) {
-    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 7) || !x || !w || !y) return YAT_EINVAL;
+    if (!y) return YAT_EINVAL;
     if (upsample != 0 && upsample != 1) return YAT_EINVAL;
     if (silu != 0 && silu != 1) return YAT_EINVAL;
     if (out_nchw != 0 && out_nchw != 1) return YAT_EINVAL;
     if (upsample && ((H | W) & 1)) return YAT_EINVAL;
     const bool small = Cout <= SMALL_COUT;
-    if (!small && ((Cout & 3) || out_nchw)) return YAT_EINVAL;
-    ConvP p{};
-    p.sc_rep = 1;
+    if (!small && out_nchw) return YAT_EINVAL;
+    conv_epilogue e{(const bf16_t*)bias, (const bf16_t*)shortcut, (const bf16_t*)residual, (bf16_t*)y, silu, shortcut_mode,
+                    shortcut_channels, 1};
     if (shortcut_mode == 1) {
         if (!shortcut || shortcut_channels <= 0 || Cout % shortcut_channels) return YAT_EINVAL;
-        p.sc_rep = Cout / shortcut_channels;
+        e.sc_rep = Cout / shortcut_channels;
     } else if (shortcut_mode == 2) {
         if (!shortcut || shortcut_channels <= 0 || ((H | W) & 1) || (4 * Cout) % shortcut_channels) return YAT_EINVAL;
-        p.sc_rep = 4 * Cout / shortcut_channels;
+        e.sc_rep = 4 * Cout / shortcut_channels;
     } else if (shortcut_mode != 0) {
         return YAT_EINVAL;
     }
     if (small && shortcut_mode) return YAT_EINVAL;
     const int Hin = upsample ? H / 2 : H, Win = upsample ? W / 2 : W;
-    const int64_t M = (int64_t)B * H * W;
-    const uint64_t x_bytes = (uint64_t)B * Hin * Win * Cin * 2, w_bytes = (uint64_t)Cout * 9 * Cin * 2;
-    if (M > 0x7fffffffll || x_bytes > 0x7fffffffull || w_bytes > 0x7fffffffull) return YAT_EINVAL;
-    if (small && w_bytes > 65536) return YAT_EINVAL;
-    p.x = (const bf16_t*)x; p.w = (const bf16_t*)w; p.bias = (const bf16_t*)bias; p.sc = (const bf16_t*)shortcut;
-    p.res = (const bf16_t*)residual; p.y = (bf16_t*)y;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.Hin = Hin; p.Win = Win; p.up = upsample; p.silu = silu;
-    p.sc_mode = shortcut_mode; p.sc_ch = shortcut_channels; p.nchw = out_nchw;
-    p.M = (int)M; p.K = 9 * Cin; p.x_bytes = x_bytes; p.w_bytes = w_bytes;
     if (small) {
-        hipLaunchKernelGGL(conv3x3_small_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), (unsigned)w_bytes,
-                           (hipStream_t)stream, p);
+        ConvGeom g;
+        if (int rc = conv_geometry(g, B, Hin, Win, H, W, Cin, Cout, upsample, x, w)) return rc;
+        if (g.w_bytes > 65536) return YAT_EINVAL;
+        hipLaunchKernelGGL(conv3x3_small_kernel, dim3((unsigned)(((int64_t)g.M + 255) / 256)), dim3(256), (unsigned)g.w_bytes,
+                           (hipStream_t)stream, g, e, out_nchw);
         YAT_CHECK_LAUNCH();
         return YAT_OK;
     }
-    p.nbm = (int)((M + CBM - 1) / CBM);
-    p.nbn = (Cout + CBN - 1) / CBN;
-    if ((int64_t)p.nbm * p.nbn > 0x7fffffffll) return YAT_EINVAL;
-    const dim3 grid((unsigned)(p.nbm * p.nbn));
-    if (Cin % 64 == 0)
-        hipLaunchKernelGGL(conv3x3_mfma_kernel<true>, grid, dim3(256), CLDS, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(conv3x3_mfma_kernel<false>, grid, dim3(256), CLDS, (hipStream_t)stream, p);
-    YAT_CHECK_LAUNCH();
-    return YAT_OK;
+    return conv3x3_launch<1, 1>(B, Hin, Win, H, W, Cin, Cout, upsample, x, w, e, stream);
 }
 
 int yat_dcae_msla_aggregate(int B, int H, int W, int C3, const void* qkv, const void* w_dw, const void* w_pw, void* out,
