@@ -151,5 +151,6 @@ def test_vae_lookup(tmp_path):
 def test_trainer_keeps_the_latent_only_path_without_a_vae(tmp_path):
     """SanaModel wires the decoder only when the pipe directory has vae/config.json (host check, no model built)."""
     import train_sana
-    assert train_sana.find_vae_dir is dcae.find_vae_dir
+    from yat_amd import dit_trainer
+    assert issubclass(train_sana.SanaModel, dit_trainer.DiTTrainer) and dit_trainer.find_vae_dir is dcae.find_vae_dir
     assert dcae.find_vae_dir(str(tmp_path / "pipe")) is None

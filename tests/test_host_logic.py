@@ -182,7 +182,7 @@ def test_host_draws_are_remembered_per_generator_state():
     from yat_amd.recipe import SanaRecipe
     from yat_amd.scheduler import FlowMatchSchedule
     r = SanaRecipe.__new__(SanaRecipe)
-    r.scheduler = FlowMatchSchedule()
+    r.scheduler, r._draw_cache = FlowMatchSchedule(), {}
     shape, B = (4, 8, 6, 10), 4
 
     def draw(gen):

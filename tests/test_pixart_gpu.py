@@ -429,6 +429,42 @@ def test_pixart_device_path_equals_autograd_path():
     assert rel(gh, 0.5 * ga.float()) <= 8e-3
 
 
+def test_pixart_optimize_device_replays_plans_under_changing_captions():
+    """``PixArtRecipe.optimize_device`` with launch plans on and off, same seeds: six steps alternating between two latent
+    buckets with captions whose lengths change every step (one of them empty in two steps, T = 300).  A recorded plan holds
+    the device addresses of the staged segments, so the steps after each bucket's first one replay only if those addresses
+    stayed put -- and are bit-identical to the unplanned run only if the staged data landed where the plan reads it."""
+    from yat_amd.pixart import PixArtConfig, PixArtTransformer2DModelHIP
+    from yat_amd.recipe import PixArtRecipe
+    cfg = PixArtConfig(num_attention_heads=2, attention_head_dim=24, in_channels=4, out_channels=8, num_layers=2,
+                       cross_attention_dim=48, sample_size=8, patch_size=2, caption_channels=64)
+    T, shapes = 300, ((8, 8), (4, 16))
+    captions = ((40, 300), (7, 129), (0, 65), (300, 1), (64, 0), (200, 13))          # B = 2 caption lengths per step
+    runs = []
+    for plans in (False, True):
+        hip = PixArtTransformer2DModelHIP(cfg, device=DEV).init_synthetic(4)
+        hip.use_plans = plans
+        recipe = PixArtRecipe(hip, pad_to=T, device=DEV)
+        g = torch.Generator().manual_seed(9)
+        torch.manual_seed(21)                     # the timestep draws (global CPU stream) and the noise (global device stream)
+        torch.cuda.manual_seed(21)
+        losses, nplans = [], []
+        for step, lens in enumerate(captions):
+            h, w = shapes[step % 2]
+            latents = (torch.randn(2, cfg.in_channels, h, w, generator=g) * 0.5).to(BF)
+            embs = [torch.randn(L, cfg.caption_channels, generator=g).to(BF) for L in lens]
+            losses.append(recipe.optimize_device(latents, embs, None))
+            nplans.append(len(hip._plans))
+        torch.cuda.synchronize()
+        runs.append((torch.stack(losses).cpu(), hip.flat_grad.clone(), getattr(hip, "plan_replays", 0), nplans))
+    (l_off, g_off, r_off, n_off), (l_on, g_on, r_on, n_on) = runs
+    print(f"[plans] pixart optimize_device: plans after each step {n_on}, {r_on} replays; losses {l_on.tolist()}")
+    assert r_off == 0 and n_off[-1] == 0
+    assert torch.isfinite(l_on.float()).all() and torch.equal(l_off, l_on) and torch.equal(g_off, g_on)
+    assert r_on >= 2 * 4                                   # steps 2..5: forward and backward replayed
+    assert n_on[1] > 0 and n_on[1:] == [n_on[1]] * 5       # nothing recorded after each bucket's first step
+
+
 def test_pixart_validation_sampler_matches_oracle():
     """CFG + DPM-Solver++ (2M) latent sampler -- the middle third of the reference's PixArt-Sigma ``validate()``
     (train_pixart_sigma.py:117-129 over the vendored denoising loop utils/patch_pixart_sigma_pipeline.py:158-208; the scheduler is

@@ -451,6 +451,42 @@ def test_sd3_launch_plan_replay_and_chains_are_bit_identical():
     assert torch.equal(l_a, l_c) and torch.equal(p_a, p_c), "two forward chains vs one differ"
 
 
+def test_sd3_optimize_device_replays_plans():
+    """``SD3Recipe.optimize_device`` with launch plans on and off, same seeds: six steps alternating between two latent
+    buckets, fixed-length prompts at a reduced token count.  The steps after each bucket's first one replay only if the staged
+    segments' device addresses stayed put, and equal the unplanned run bit for bit only if the data landed there."""
+    from yat_amd.recipe import SD3Recipe
+    from yat_amd.sd3 import SD3Config, SD3Transformer2DModelHIP
+    cfg = SD3Config(sample_size=16, patch_size=2, in_channels=8, out_channels=8, num_layers=2, attention_head_dim=64,
+                    num_attention_heads=2, joint_attention_dim=96, caption_projection_dim=128, pooled_projection_dim=64,
+                    pos_embed_max_size=24, dual_attention_layers=(0,))
+    T, shapes = 10, ((8, 8), (4, 16))
+    runs = []
+    for plans in (False, True):
+        hip = SD3Transformer2DModelHIP(cfg, device=DEV).init_synthetic(4)
+        hip.use_plans = plans
+        recipe = SD3Recipe(hip, device=DEV)
+        g = torch.Generator().manual_seed(9)
+        torch.manual_seed(21)                     # the timestep draws (global CPU stream) and the noise (global device stream)
+        torch.cuda.manual_seed(21)
+        losses, nplans = [], []
+        for step in range(6):
+            h, w = shapes[step % 2]
+            latents = (torch.randn(2, cfg.in_channels, h, w, generator=g) * 0.5).to(BF)
+            embs = [(torch.randn(T, cfg.joint_attention_dim, generator=g).to(BF),
+                     torch.randn(cfg.pooled_projection_dim, generator=g).to(BF)) for _ in range(2)]
+            losses.append(recipe.optimize_device(latents, embs, None))
+            nplans.append(len(hip._plans))
+        torch.cuda.synchronize()
+        runs.append((torch.stack(losses).cpu(), hip.flat_grad.clone(), getattr(hip, "plan_replays", 0), nplans))
+    (l_off, g_off, r_off, n_off), (l_on, g_on, r_on, n_on) = runs
+    print(f"[plans] sd3 optimize_device: plans after each step {n_on}, {r_on} replays; losses {l_on.tolist()}")
+    assert r_off == 0 and n_off[-1] == 0
+    assert torch.isfinite(l_on.float()).all() and torch.equal(l_off, l_on) and torch.equal(g_off, g_on)
+    assert r_on >= 2 * 4                                   # steps 2..5: forward and backward replayed
+    assert n_on[1] > 0 and n_on[1:] == [n_on[1]] * 5       # nothing recorded after each bucket's first step
+
+
 def test_sd3_device_path_equals_autograd_path():
     """``SD3Recipe.optimize_device`` (what ``SD35Trainer.optimize`` runs when training) against ``optimize`` +
     ``loss.backward()`` on the same host batch and global RNG state (train_sd35.py:180,182): loss and every gradient

@@ -206,8 +206,9 @@ def test_vae_kl_entry_points_reject_bad_arguments(built_lib):
 
 
 # ------------------------------------------------------------------------------------------------ trainer validate() wiring
-def _fake_trainer(tmp_path, vae_dir, side):
-    out = types.SimpleNamespace(
+def _fake_trainer(cls, tmp_path, vae_dir, side):
+    out = cls.__new__(cls)                                      # host check only: no model, no device
+    out.__dict__.update(
         params=types.SimpleNamespace(local_shard_paths=[str(tmp_path / "shard-000000.tar")], validation_prompts=["a red fox"]),
         accelerator=types.SimpleNamespace(device="cpu"), global_step=7, logger=None, vae_dir=vae_dir, vae=None,
         model=types.SimpleNamespace(config=types.SimpleNamespace(sample_size=side), cfg=types.SimpleNamespace(sample_size=side)),
@@ -234,23 +235,23 @@ def test_trainers_decode_only_with_a_vae_dir(tmp_path, monkeypatch, module, cls,
     """validate() without a VAE directory keeps the latent-only path (latents saved, no decoder built, no PNG); with one it
     builds the decoder once (load_vae_decoder) and writes models/<step>/validation_{idx}.png after the latents."""
     sys.path.insert(0, ROOT)
-    mod = __import__(module)
-    from yat_amd import sampler as smp
+    trainer_cls = getattr(__import__(module), cls)
+    from yat_amd import dit_trainer, sampler as smp
     side = 4
     monkeypatch.setattr(smp, sampler, lambda *a, **k: torch.randn(1, channels, side, side).to(torch.bfloat16))
     torch.save([tuple(torch.zeros(1, 2) for _ in range(4))], tmp_path / "validation_embeds.pt")
     monkeypatch.chdir(tmp_path)
-    validate = getattr(mod, cls).validate
+    validate = trainer_cls.validate
     built = []
     dec = _FakeDecoder()
-    monkeypatch.setattr(mod, "load_vae_decoder", lambda d, device: built.append(d) or dec)
+    monkeypatch.setattr(dit_trainer, "load_vae_decoder", lambda d, device: built.append(d) or dec)
 
-    t = _fake_trainer(tmp_path, None, side)
+    t = _fake_trainer(trainer_cls, tmp_path, None, side)
     out = validate(t)
     assert len(out) == 1 and (tmp_path / "models" / "7" / "validation_latents.pt").exists()
     assert not (tmp_path / "models" / "7" / "validation_0.png").exists() and built == [] and t.vae is None
 
-    t = _fake_trainer(tmp_path, str(tmp_path / "vae"), side)
+    t = _fake_trainer(trainer_cls, tmp_path, str(tmp_path / "vae"), side)
     validate(t)
     validate(t)
     assert built == [str(tmp_path / "vae")] and t.vae is dec and dec.calls == [(1, channels, side, side)] * 2
@@ -261,6 +262,7 @@ def test_trainers_look_up_the_vae_like_sana():
     sys.path.insert(0, ROOT)
     import train_pixart_sigma
     import train_sd35
-    from yat_amd import dcae
-    assert train_pixart_sigma.find_vae_dir is dcae.find_vae_dir and train_sd35.find_vae_dir is dcae.find_vae_dir
-    assert train_pixart_sigma.load_vae_decoder is kl.load_vae_decoder and train_sd35.load_vae_decoder is kl.load_vae_decoder
+    from yat_amd import dcae, dit_trainer
+    for cls in (train_pixart_sigma.PixartSigmaTrainer, train_sd35.SD35Trainer):        # the lookup lives in the shared base
+        assert issubclass(cls, dit_trainer.DiTTrainer) and cls.validate is dit_trainer.DiTTrainer.validate
+    assert dit_trainer.find_vae_dir is dcae.find_vae_dir and dit_trainer.load_vae_decoder is kl.load_vae_decoder

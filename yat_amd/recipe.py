@@ -11,6 +11,7 @@ buffer, ONE H2D copy and one ``yat_pad_mask`` launch; ``get_sigmas``' B device->
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -18,24 +19,47 @@ import torch
 from . import ops
 from .scheduler import DDPMSchedule, FlowMatchSchedule
 
-BF16 = torch.bfloat16
+BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
 
-class _MseLoss(torch.autograd.Function):
-    """mean((pred.float() - target.float())**2) with the gradient produced in the same launch."""
+class _FusedMse(torch.autograd.Function):
+    """A mean-squared-error kernel whose launch also produces the gradient, as an autograd node.  ``kernel`` /
+    ``dtype``: ``ops.mse_fwd_bwd`` / fp32 -- mean((pred.float() - target.float())**2) (SANA); ``ops.mse_bf16_chunk`` / bf16 --
+    MSELoss()(out.chunk(2, 1)[0], noise) evaluated in bf16, gradient zero on the dropped half (PixArt; SD3.5 over the whole
+    tensor)."""
 
     @staticmethod
-    def forward(ctx, pred, target, ws):
-        loss = torch.zeros(1, dtype=torch.float32, device=pred.device)
+    def forward(ctx, pred, target, ws, kernel, dtype):
+        loss = torch.zeros(1, dtype=F32, device=pred.device)
         dpred = torch.empty_like(pred)
-        ops.mse_fwd_bwd(pred.contiguous(), target, loss, dpred, ws)
+        kernel(pred.contiguous(), target, loss, dpred, ws)
         ctx.save_for_backward(dpred)
-        return loss[0]
+        return loss[0].to(dtype)
 
     @staticmethod
     def backward(ctx, g):
         (dpred,) = ctx.saved_tensors
-        return dpred * g.to(dpred.dtype), None, None
+        return dpred * g.to(dpred.dtype), None, None, None, None
+
+
+class _Layout:
+    """A step's staging buffer as named segments, declared once as (name, shape, dtype) in buffer order: every start is
+    16-byte aligned, and a start depends only on the segments declared before it.  A recipe therefore declares its fixed-size
+    segments first and the ragged text rows last: for a given bucket shape the device addresses of the fixed-size segments --
+    which recorded launch plans hold -- then stay put from batch to batch.  ``spare``: bytes the last segment may still
+    grow by (the longest possible captions), so ``capacity`` is the most this bucket shape ever stages."""
+
+    def __init__(self, segments, spare=0):
+        self.spec, o = {}, 0
+        for name, shape, dtype in segments:
+            n = math.prod(shape) * dtype.itemsize
+            self.spec[name] = (o, n, dtype, tuple(shape))
+            o += (n + 15) & ~15
+        self.total, self.capacity = o, o + spare
+
+    def views(self, buf):
+        """name -> that segment of ``buf`` (any uint8 tensor of at least ``total`` bytes) in its dtype and shape."""
+        return {name: buf[o:o + n].view(dtype).view(shape) for name, (o, n, dtype, shape) in self.spec.items()}
 
 
 class _Stager:
@@ -47,20 +71,22 @@ class _Stager:
 
     def __init__(self, dev):
         self.dev, self.pin, self.ev, self.k, self.land = dev, [None, None], [None, None], 0, None
+        self.cap, self.layout = 0, None
 
-    def begin(self, nbytes, capacity=0):
-        """``capacity``: the most this caller will ever stage for the current shapes -- buffers are sized for it at once, so
-        their addresses (which recorded launch plans hold) do not move when a longer caption arrives."""
+    def begin(self, layout):
+        """-> the pinned host views of ``layout``'s segments.  Buffers are sized for ``layout.capacity`` at once, so their
+        addresses (which recorded launch plans hold) do not move when a longer caption arrives."""
         k = self.k
         if self.ev[k] is not None:
             self.ev[k].synchronize()
-        self.cap = max(getattr(self, "cap", 0), capacity, nbytes)
+        self.layout, self.cap = layout, max(self.cap, layout.capacity)
         if self.pin[k] is None or self.pin[k].numel() < self.cap:
             self.pin[k] = torch.empty(self.cap, dtype=torch.uint8).pin_memory()
-        return self.pin[k]
+        return layout.views(self.pin[k])
 
-    def commit(self, nbytes):
-        k = self.k
+    def commit(self):
+        """The one copy of what ``begin``'s views were filled with -> the device views of the same segments."""
+        k, nbytes = self.k, self.layout.total
         if self.land is None or self.land.numel() < self.cap:
             self.land = torch.empty(self.cap, dtype=torch.uint8, device=self.dev)
         self.land[:nbytes].copy_(self.pin[k][:nbytes], non_blocking=True)
@@ -68,7 +94,7 @@ class _Stager:
         ev.record()
         self.ev[k] = ev
         self.k ^= 1
-        return self.land
+        return self.layout.views(self.land)
 
 
 def _pack_rows(embeddings, dst):
@@ -91,32 +117,121 @@ def _report_loss(model, loss):
         hook(loss)
 
 
-def _layout(sizes):
-    """16-byte aligned offsets of consecutive byte segments -> (offsets, total)."""
-    offs, o = [], 0
-    for n in sizes:
-        offs.append(o)
-        o += (n + 15) & ~15
-    return offs, o
+def _cpu_generator(generator):
+    return generator if (generator is not None and generator.device.type == "cpu") else None
 
 
-class SanaRecipe:
-    def __init__(self, model, scheduler: FlowMatchSchedule | None = None, pad_to: int = 512, device="cuda"):
+def kv_work_pairs(lens, T, empty_attends_all):
+    """The dK/dV work list (``ops.kv_work_list``) on the host: one (image, 64-key tile) pair per tile that holds keys.  An
+    empty caption attends to all ``T`` padding rows in the padded layout PixArt-Sigma trains on (``empty_attends_all``); in
+    SANA's list it has no tile."""
+    return [(b, t) for b, L in enumerate(lens) for t in range(((T if empty_attends_all and L == 0 else L) + 63) // 64)]
+
+
+class _Recipe:
+    """What the three recipes share: the device, the loss workspace and output, persistent scratch buffers, the stager of the
+    device path and the staging of ragged captions."""
+
+    def __init__(self, model, scheduler, device, pad_to=None):
         self.model = model
-        self.scheduler = scheduler or FlowMatchSchedule()
-        self.pad_to = pad_to
+        self.scheduler = scheduler
+        self.pad_to = pad_to        # rows the ragged captions are padded to; None: fixed-length prompts
         self.dev = torch.device(device)
-        self._mse_ws = torch.empty(256, dtype=torch.float32, device=self.dev)
+        self._mse_ws = torch.empty(256, dtype=F32, device=self.dev)
+        self._loss_out = torch.zeros(1, dtype=F32, device=self.dev)
+        self._stager = _Stager(self.dev)
+        self._scratch_cache = {}
+        self._fixed = None          # pad / mask outputs of the device path, per (B, T, C)
+
+    def _scratch(self, name, like):
+        """One persistent buffer per (name, shape): a bucket that comes back finds its buffers at the same addresses."""
+        key = (name, tuple(like.shape), like.dtype)
+        t = self._scratch_cache.get(key)
+        if t is None:
+            t = self._scratch_cache[key] = torch.empty_like(like)
+        return t
+
+    @staticmethod
+    def _host_batch(latents, text):
+        if latents.is_cuda or text.is_cuda:
+            raise ValueError("optimize_device stages host batches (the sampler yields CPU tensors)")
+
+    def _caption_lens(self, embeddings):
+        lens = [int(e.shape[0]) for e in embeddings]
+        if max(lens) > self.pad_to:
+            raise ValueError(f"embedding longer than pad length {self.pad_to}")
+        return lens
+
+    # ---- ragged captions on the device path (SANA, PixArt): offsets, dK/dV work list, rows -> pad / mask
+    def _stage_text(self, host, embeddings, lens, empty_attends_all):
+        """Fills the "off", "work" and "emb" segments -> the number of work-list pairs."""
+        offs = [0]
+        for L in lens:
+            offs.append(offs[-1] + L)
+        host["off"].copy_(torch.tensor(offs, dtype=I32))
+        pairs = kv_work_pairs(lens, self.pad_to, empty_attends_all)
+        host["work"][:len(pairs)].copy_(torch.tensor(pairs, dtype=I32).reshape(len(pairs), 2))
+        if offs[-1]:
+            _pack_rows(embeddings, host["emb"])
+        return len(pairs)
+
+    def _pad_text(self, dev, B, C, packed_enc=None):
+        """The staged rows -> (enc, bias, kv_len, kv_off): the reference's padded [B, T, C] batch in persistent buffers
+        (``kv_off`` None), or packed into ``packed_enc``, with each image's first row."""
+        T = self.pad_to
+        if self._fixed is None or self._fixed[0].shape != (B, T, C):
+            self._fixed = (torch.empty(B, T, C, dtype=BF16, device=self.dev), torch.empty(B, T, dtype=torch.int64, device=self.dev),
+                           torch.empty(B, T, dtype=F32, device=self.dev), torch.empty(B, dtype=I32, device=self.dev))
+        enc, mask, bias, kvl = self._fixed
+        if packed_enc is not None:
+            ops.pack_mask(dev["emb"], dev["off"], B, T, C, packed_enc, mask, bias, kvl)
+            return packed_enc, bias, kvl, dev["off"][:B]
+        ops.pad_mask(dev["emb"], dev["off"], B, T, C, enc, mask, bias, kvl)
+        return enc, bias, kvl, None
+
+    # ---- draws from the global RNG streams (PixArt, SD3.5); a generator, when given, replaces them
+    def _draw_global(self, shape, generator, noise, fields):
+        """-> (noise, *``scheduler.sample``'s ``fields``) on the device."""
+        if noise is None:
+            if generator is not None and generator.device.type != "cuda":
+                noise = torch.randn(shape, generator=generator, device="cpu", dtype=BF16).to(self.dev, non_blocking=True)
+            else:
+                noise = torch.randn(shape, generator=generator, device=self.dev, dtype=BF16)
+        drawn = self.scheduler.sample(shape[0], _cpu_generator(generator))[fields]
+        return (noise.to(self.dev), *(x.to(self.dev, non_blocking=True) for x in drawn))
+
+    @staticmethod
+    def _host_noise(cpu_gen, host):
+        """The device path's noise, host half: a CPU generator draws it into the staged "noise" segment -- before
+        ``scheduler.sample`` draws from the same generator, the reference's order."""
+        if cpu_gen is not None:
+            torch.randn(host["noise"].shape, generator=cpu_gen, dtype=BF16, out=host["noise"])
+
+    def _device_noise(self, generator, dev):
+        """... and the device half, after the copy: the staged draw, or else a draw on the device (from the global stream as
+        the reference draws it, or from a device generator) into a persistent buffer."""
+        if _cpu_generator(generator) is not None:
+            return dev["noise"]
+        noise = self._scratch("_noise_buf", dev["lat"])
+        torch.randn(noise.shape, generator=generator, device=self.dev, dtype=BF16, out=noise)
+        return noise
+
+
+class SanaRecipe(_Recipe):
+    COEFS = ("sig",)            # the per-sample bf16 coefficients ``scheduler.sample`` yields beside the timestep
+
+    def __init__(self, model, scheduler: FlowMatchSchedule | None = None, pad_to: int = 512, device="cuda"):
+        super().__init__(model, scheduler or FlowMatchSchedule(), device, pad_to)
         self._pin = None
+        self._packed_buf = None
+        self._draw_cache = {}
         self.device_rng = None     # torch.Generator(device) for the throughput mode
 
     # ---- text embeddings: ragged list -> padded [B, T, C] + mask/bias/kv_len on device (one H2D)
     def pad_embeddings(self, embeddings):
         B, T = len(embeddings), self.pad_to
         C = embeddings[0].shape[1]
-        lens = [int(e.shape[0]) for e in embeddings]
-        if max(lens) > T:
-            raise ValueError(f"embedding longer than pad length {T}")
+        lens = self._caption_lens(embeddings)
         offs = [0]
         for L in lens:
             offs.append(offs[-1] + L)
@@ -144,8 +259,7 @@ class SanaRecipe:
         B = shape[0]
         if generator is not None and generator.device.type == "cuda":
             noise = torch.randn(shape, generator=generator, device=self.dev, dtype=BF16)
-            cpu_gen = getattr(self, "_cpu_gen", None)
-            idx, t, sig = self.scheduler.sample(B, cpu_gen)
+            idx, t, sig = self.scheduler.sample(B, None)
         else:
             noise = torch.randn(shape, generator=generator, device="cpu", dtype=BF16).to(self.dev, non_blocking=True)
             idx, t, sig = self.scheduler.sample(B, generator)
@@ -159,7 +273,7 @@ class SanaRecipe:
         noisy, target = ops.flow_mix(latents, noise, sigmas)
         self.model.next_kv_work = self.kv_work
         pred = self.model(noisy, encoder_hidden_states=enc, timestep=timesteps, encoder_attention_mask=mask).sample
-        loss = _MseLoss.apply(pred, target, self._mse_ws)
+        loss = _FusedMse.apply(pred, target, self._mse_ws, ops.mse_fwd_bwd, F32)
         return (loss, pred, target) if return_pred else loss
 
     # ---- packed text rows (no padding rows through the text-side GEMMs; SanaTransformer2DModelHIP.forward_impl)
@@ -180,10 +294,9 @@ class SanaRecipe:
     def packed_enc(self, B, T, C, rows):
         """[packed_rows(rows), C] view of one persistent buffer sized for B * T rows (its address never moves)."""
         cap = self.packed_rows(B * T)
-        buf = getattr(self, "_packed_buf", None)
-        if buf is None or buf.shape != (cap, C):
-            buf = self._packed_buf = torch.empty(cap, C, dtype=BF16, device=self.dev)
-        return buf[:self.packed_rows(rows)]
+        if self._packed_buf is None or self._packed_buf.shape != (cap, C):
+            self._packed_buf = torch.empty(cap, C, dtype=BF16, device=self.dev)
+        return self._packed_buf[:self.packed_rows(rows)]
 
     def train_step_device(self, latents, enc, mask_bias_kvl, noise, timesteps, sigmas, loss_out, kv_work=None, gscale=1.0,
                           kv_off=None):
@@ -213,60 +326,28 @@ class SanaRecipe:
         CPU as the reference draws them), but the host side is one packed pinned buffer and ONE H2D copy, and forward, loss,
         dL/dpred (scaled by ``gscale`` = 1 / gradient_accumulation_steps) and backward are straight-line C-ABI launches with
         no autograd objects.  -> loss (0-dim fp32 device tensor); the gradients are already in the flat gradient buffer."""
-        if latents.is_cuda or embeddings[0].is_cuda:
-            raise ValueError("optimize_device stages host batches (the sampler yields CPU tensors)")
-        B, T = len(embeddings), self.pad_to
-        C = embeddings[0].shape[1]
-        lens = [int(e.shape[0]) for e in embeddings]
-        if max(lens) > T:
-            raise ValueError(f"embedding longer than pad length {T}")
-        rows = sum(lens)
-        pairs = [(b, t) for b, L in enumerate(lens) for t in range((L + 63) // 64)]          # dK/dV work list (ops.kv_work_list)
-        nlat = latents.numel()
-        max_pairs = B * ((T + 63) // 64)
-        # fixed-size segments first (their device addresses then depend on the bucket shape only: a recorded launch plan
-        # stays valid from batch to batch); the ragged text rows go last
-        (o_lat, o_noise, o_off, o_t, o_sig, o_work, o_emb), total = _layout(
-            [2 * nlat, 2 * nlat, 4 * (B + 1), 4 * B, 2 * B, 8 * max_pairs, 2 * rows * C])
-        st = self._stager = getattr(self, "_stager", None) or _Stager(self.dev)
-        pin = st.begin(total, capacity=total + 2 * (B * T - rows) * C)
+        self._host_batch(latents, embeddings[0])
+        B, C, lens = len(embeddings), embeddings[0].shape[1], self._caption_lens(embeddings)
+        host = self._stager.begin(self._layout(latents.shape, B, C, sum(lens)))
+        host["lat"].copy_(latents)
+        t, sig = self._draw_cached(latents.shape, B, generator, host["noise"])                                      # :183-204
+        host["t"].copy_(t)
+        host["sig"].copy_(sig)
+        npairs = self._stage_text(host, embeddings, lens, empty_attends_all=False)
+        dev = self._stager.commit()
+        packed = self.packed_enc(B, self.pad_to, C, sum(lens)) if self.packs_text(lens) else None
+        enc, bias, kvl, kv_off = self._pad_text(dev, B, C, packed)                       # :168-180 (packed: minus the padding rows)
+        self.train_step_device(dev["lat"], enc, (bias, kvl), dev["noise"], dev["t"], dev["sig"], self._loss_out,
+                               kv_work=dev["work"][:npairs], gscale=gscale, kv_off=kv_off)
+        return self._loss_out[0].clone()
 
-        def seg(o, n, dtype):
-            return pin[o:o + n].view(dtype)
-        seg(o_lat, 2 * nlat, BF16).view(latents.shape).copy_(latents)
-        t, sig = self._draw_cached(latents.shape, B, generator, seg(o_noise, 2 * nlat, BF16).view(latents.shape))      # :183-204
-        _pack_rows(embeddings, seg(o_emb, 2 * rows * C, BF16).view(rows, C))
-        offs = [0]
-        for L in lens:
-            offs.append(offs[-1] + L)
-        seg(o_off, 4 * (B + 1), torch.int32).copy_(torch.tensor(offs, dtype=torch.int32))
-        seg(o_t, 4 * B, torch.float32).copy_(t)
-        seg(o_sig, 2 * B, BF16).copy_(sig)
-        seg(o_work, 8 * len(pairs), torch.int32).copy_(torch.tensor(pairs, dtype=torch.int32).flatten())
-        land = st.commit(total)
-
-        def dseg(o, n, dtype):
-            return land[o:o + n].view(dtype)
-        lat_d = dseg(o_lat, 2 * nlat, BF16).view(latents.shape)
-        noise_d = dseg(o_noise, 2 * nlat, BF16).view(latents.shape)
-        fixed = getattr(self, "_fixed", None)
-        if fixed is None or fixed[0].shape != (B, T, C):
-            fixed = self._fixed = (torch.empty(B, T, C, dtype=BF16, device=self.dev),
-                                   torch.empty(B, T, dtype=torch.int64, device=self.dev),
-                                   torch.empty(B, T, dtype=torch.float32, device=self.dev),
-                                   torch.empty(B, dtype=torch.int32, device=self.dev),
-                                   torch.zeros(1, dtype=torch.float32, device=self.dev))
-        enc, mask, bias, kvl, loss_out = fixed
-        src_d, off_d, kv_off = dseg(o_emb, 2 * rows * C, BF16).view(rows, C), dseg(o_off, 4 * (B + 1), torch.int32), None
-        if self.packs_text(lens):
-            enc, kv_off = self.packed_enc(B, T, C, rows), off_d[:B]
-            ops.pack_mask(src_d, off_d, B, T, C, enc, mask, bias, kvl)                                                   # :168-180,
-        else:                                                                                    # minus the padding rows
-            ops.pad_mask(src_d, off_d, B, T, C, enc, mask, bias, kvl)                                                    # :168-180
-        self.train_step_device(lat_d, enc, (bias, kvl), noise_d, dseg(o_t, 4 * B, torch.float32), dseg(o_sig, 2 * B, BF16),
-                               loss_out, kv_work=dseg(o_work, 8 * len(pairs), torch.int32).view(len(pairs), 2), gscale=gscale,
-                               kv_off=kv_off)
-        return loss_out[0].clone()
+    def _layout(self, shape, B, C, rows, host_noise=True):
+        """The device path's staging segments.  Fixed-size segments first, the ragged text rows last, capacity for B captions
+        of ``pad_to`` rows: see ``_Layout``."""
+        T = self.pad_to
+        return _Layout([("lat", shape, BF16), ("noise", shape if host_noise else (0,), BF16), ("off", (B + 1,), I32), ("t", (B,), F32),
+                        *((name, (B,), BF16) for name in self.COEFS), ("work", (B * ((T + 63) // 64), 2), I32),
+                        ("emb", (rows, C), BF16)], spare=2 * (B * T - rows) * C)
 
     def _draw_cached(self, shape, B, generator, noise_out):
         """The step's host draws -- bf16 noise of ``shape`` into ``noise_out``, then the logit-normal timestep indices (-> t,
@@ -281,7 +362,7 @@ class SanaRecipe:
             torch.randn(shape, dtype=BF16, out=noise_out)
             _, t, sig = self.scheduler.sample(B, None)
             return t, sig
-        cache = self.__dict__.setdefault("_draw_cache", {})
+        cache = self._draw_cache
         key = (tuple(shape), B)
         state = generator.get_state()
         hit = cache.get(key)
@@ -293,15 +374,6 @@ class SanaRecipe:
         _, t, sig = self.scheduler.sample(B, generator)
         cache[key] = (state, noise_out.clone(), t.clone(), sig.clone(), generator.get_state())
         return t, sig
-
-    def _scratch(self, name, like):
-        """One persistent buffer per (name, shape): a bucket that comes back finds its buffers at the same addresses."""
-        cache = self.__dict__.setdefault("_scratch_cache", {})
-        key = (name, tuple(like.shape), like.dtype)
-        t = cache.get(key)
-        if t is None:
-            t = cache[key] = torch.empty_like(like)
-        return t
 
     def _noisy(self, like):
         return self._scratch("_noisy_buf", like)
@@ -319,6 +391,8 @@ class PixArtRecipe(SanaRecipe):
     ``add_noise`` (:176) -> model (:178-182) -> ``.chunk(2, 1)[0]`` against the noise, MSE evaluated in bf16 (:183-184).
     The pad / mask staging is SanaRecipe's; mix and loss(+dL/dpred) are one launch each."""
 
+    COEFS = ("a", "c")
+
     def __init__(self, model, scheduler: DDPMSchedule | None = None, pad_to: int = 300, device="cuda"):
         super().__init__(model, scheduler or DDPMSchedule(), pad_to=pad_to, device=device)
 
@@ -326,15 +400,7 @@ class PixArtRecipe(SanaRecipe):
         """The reference draws the noise on the device from the global RNG (randn_tensor without a generator, :170) and the
         timestep indices on the host from the global CPU RNG (:172); a generator, when given, replaces the global streams
         (device generator -> noise, CPU generator -> both)."""
-        if noise is None:
-            if generator is not None and generator.device.type != "cuda":
-                noise = torch.randn(shape, generator=generator, device="cpu", dtype=BF16).to(self.dev, non_blocking=True)
-            else:
-                noise = torch.randn(shape, generator=generator, device=self.dev, dtype=BF16)
-        cpu_gen = generator if (generator is not None and generator.device.type == "cpu") else None
-        t, a, c = self.scheduler.sample(shape[0], cpu_gen)
-        return noise.to(self.dev), t.to(self.dev, non_blocking=True), a.to(self.dev, non_blocking=True), \
-            c.to(self.dev, non_blocking=True)
+        return self._draw_global(shape, generator, noise, slice(0, 3))
 
     def optimize(self, latents, embeddings, generator=None, return_pred=False, noise=None):
         enc, mask, bias, kvl = self.pad_embeddings(embeddings)
@@ -343,7 +409,7 @@ class PixArtRecipe(SanaRecipe):
         noisy = ops.ddpm_add_noise(latents, noise, a, c)
         self.model.next_kv_work = self.kv_work
         out = self.model(noisy, encoder_hidden_states=enc, timestep=timesteps, encoder_attention_mask=mask).sample
-        loss = _MseBf16Chunk.apply(out, noise, self._mse_ws)
+        loss = _FusedMse.apply(out, noise, self._mse_ws, ops.mse_bf16_chunk, BF16)
         return (loss, out, noise) if return_pred else loss
 
     def train_step_device(self, latents, enc, mask_bias_kvl, noise, timesteps, coef_a, coef_c, loss_out, kv_work=None,
@@ -367,85 +433,26 @@ class PixArtRecipe(SanaRecipe):
         generator, when given, draws it on the host in the reference's order instead); pad / mask, add_noise, forward, bf16
         loss + dL/dpred and backward are straight-line launches replayed from a launch plan.  -> loss (0-dim bf16 device
         tensor, as the reference's ``MSELoss`` on bf16 operands returns); gradients are in the flat gradient buffer."""
-        if latents.is_cuda or embeddings[0].is_cuda:
-            raise ValueError("optimize_device stages host batches (the sampler yields CPU tensors)")
-        B, T = len(embeddings), self.pad_to
-        C = embeddings[0].shape[1]
-        lens = [int(e.shape[0]) for e in embeddings]
-        if max(lens) > T:
-            raise ValueError(f"embedding longer than pad length {T}")
-        rows = sum(lens)
-        pairs = [(b, t) for b, L in enumerate(lens) for t in range(((L if L > 0 else T) + 63) // 64)]     # ops.kv_work_list
-        nlat = latents.numel()
-        max_pairs = B * ((T + 63) // 64)
-        cpu_gen = generator if (generator is not None and generator.device.type == "cpu") else None
-        host_noise = cpu_gen is not None
-        (o_lat, o_noise, o_off, o_t, o_a, o_c, o_work, o_emb), total = _layout(
-            [2 * nlat, 2 * nlat if host_noise else 0, 4 * (B + 1), 4 * B, 2 * B, 2 * B, 8 * max_pairs, 2 * rows * C])
-        st = self._stager = getattr(self, "_stager", None) or _Stager(self.dev)
-        pin = st.begin(total, capacity=total + 2 * (B * T - rows) * C)
-
-        def seg(o, n, dtype):
-            return pin[o:o + n].view(dtype)
-        seg(o_lat, 2 * nlat, BF16).view(latents.shape).copy_(latents)
-        if host_noise:                                                                                           # :170
-            torch.randn(latents.shape, generator=cpu_gen, dtype=BF16, out=seg(o_noise, 2 * nlat, BF16).view(latents.shape))
+        self._host_batch(latents, embeddings[0])
+        B, C, lens = len(embeddings), embeddings[0].shape[1], self._caption_lens(embeddings)
+        cpu_gen = _cpu_generator(generator)
+        host = self._stager.begin(self._layout(latents.shape, B, C, sum(lens), host_noise=cpu_gen is not None))
+        host["lat"].copy_(latents)
+        self._host_noise(cpu_gen, host)                                                                          # :170
         t, a, c = self.scheduler.sample(B, cpu_gen)                                                              # :172-174
-        if rows:
-            _pack_rows(embeddings, seg(o_emb, 2 * rows * C, BF16).view(rows, C))
-        offs = [0]
-        for L in lens:
-            offs.append(offs[-1] + L)
-        seg(o_off, 4 * (B + 1), torch.int32).copy_(torch.tensor(offs, dtype=torch.int32))
-        seg(o_t, 4 * B, torch.float32).copy_(t)                     # int64 timestep -> the float the embedder takes (exact)
-        seg(o_a, 2 * B, BF16).copy_(a)
-        seg(o_c, 2 * B, BF16).copy_(c)
-        seg(o_work, 8 * len(pairs), torch.int32).copy_(torch.tensor(pairs, dtype=torch.int32).flatten())
-        land = st.commit(total)
-
-        def dseg(o, n, dtype):
-            return land[o:o + n].view(dtype)
-        lat_d = dseg(o_lat, 2 * nlat, BF16).view(latents.shape)
-        if host_noise:
-            noise_d = dseg(o_noise, 2 * nlat, BF16).view(latents.shape)
-        else:
-            noise_d = self._scratch("_noise_buf", lat_d)
-            dev_gen = generator if (generator is not None and generator.device.type == "cuda") else None
-            torch.randn(latents.shape, generator=dev_gen, device=self.dev, dtype=BF16, out=noise_d)              # :170
-        fixed = getattr(self, "_fixed", None)
-        if fixed is None or fixed[0].shape != (B, T, C):
-            fixed = self._fixed = (torch.empty(B, T, C, dtype=BF16, device=self.dev),
-                                   torch.empty(B, T, dtype=torch.int64, device=self.dev),
-                                   torch.empty(B, T, dtype=torch.float32, device=self.dev),
-                                   torch.empty(B, dtype=torch.int32, device=self.dev),
-                                   torch.zeros(1, dtype=torch.float32, device=self.dev))
-        enc, mask, bias, kvl, loss_out = fixed
-        ops.pad_mask(dseg(o_emb, 2 * rows * C, BF16).view(rows, C), dseg(o_off, 4 * (B + 1), torch.int32), B, T, C, enc, mask,
-                     bias, kvl)                                                                                  # :158-168
-        self.train_step_device(lat_d, enc, (bias, kvl), noise_d, dseg(o_t, 4 * B, torch.float32), dseg(o_a, 2 * B, BF16),
-                               dseg(o_c, 2 * B, BF16), loss_out,
-                               kv_work=dseg(o_work, 8 * len(pairs), torch.int32).view(len(pairs), 2), gscale=gscale)
-        return loss_out[0].to(BF16)
+        host["t"].copy_(t)                                          # int64 timestep -> the float the embedder takes (exact)
+        host["a"].copy_(a)
+        host["c"].copy_(c)
+        npairs = self._stage_text(host, embeddings, lens, empty_attends_all=True)
+        dev = self._stager.commit()
+        noise = self._device_noise(generator, dev)                                                               # :170
+        enc, bias, kvl, _ = self._pad_text(dev, B, C)                                                            # :158-168
+        self.train_step_device(dev["lat"], enc, (bias, kvl), noise, dev["t"], dev["a"], dev["c"], self._loss_out,
+                               kv_work=dev["work"][:npairs], gscale=gscale)
+        return self._loss_out[0].to(BF16)
 
 
-class _MseBf16Chunk(torch.autograd.Function):
-    """MSELoss()(out.chunk(2, 1)[0], noise) in bf16, with the gradient (zero on the dropped half) from the same launch."""
-
-    @staticmethod
-    def forward(ctx, out, target, ws):
-        loss = torch.zeros(1, dtype=torch.float32, device=out.device)
-        dpred = torch.empty_like(out)
-        ops.mse_bf16_chunk(out.contiguous(), target, loss, dpred, ws)
-        ctx.save_for_backward(dpred)
-        return loss[0].to(BF16)
-
-    @staticmethod
-    def backward(ctx, g):
-        (dpred,) = ctx.saved_tensors
-        return dpred * g.to(dpred.dtype), None, None
-
-
-class SD3Recipe:
+class SD3Recipe(_Recipe):
     """``SD35Trainer.optimize`` (train_sd35.py:165-194) on the HIP path: noise in the latents' dtype from the global RNG on the
     device (:180, ``randn_tensor`` without a generator) -> logit-normal u on the CPU (:182) -> indices (:183) ->
     ``scheduler.timesteps[indices]`` (:184) -> ``scheduler.scale_noise`` (:185) = sigma n + (1 - sigma) x in bf16 [RECALL] ->
@@ -455,20 +462,10 @@ class SD3Recipe:
     (device generator -> noise, CPU generator -> noise and u) so tests can pin the draws."""
 
     def __init__(self, model, scheduler: FlowMatchSchedule | None = None, device="cuda"):
-        self.model = model
-        self.scheduler = scheduler or FlowMatchSchedule(shift=3.0)
-        self.dev = torch.device(device)
-        self._mse_ws = torch.empty(256, dtype=torch.float32, device=self.dev)
+        super().__init__(model, scheduler or FlowMatchSchedule(shift=3.0), device)
 
     def draw(self, shape, generator=None, noise=None):
-        if noise is None:
-            if generator is not None and generator.device.type != "cuda":
-                noise = torch.randn(shape, generator=generator, device="cpu", dtype=BF16).to(self.dev, non_blocking=True)
-            else:
-                noise = torch.randn(shape, generator=generator, device=self.dev, dtype=BF16)
-        cpu_gen = generator if (generator is not None and generator.device.type == "cpu") else None
-        _, t, sig = self.scheduler.sample(shape[0], cpu_gen)
-        return noise.to(self.dev), t.to(self.dev, non_blocking=True), sig.to(self.dev, non_blocking=True)
+        return self._draw_global(shape, generator, noise, slice(1, 3))
 
     @staticmethod
     def stack_embeddings(embeddings):
@@ -486,7 +483,7 @@ class SD3Recipe:
         noisy, target = ops.flow_mix(latents, noise, sigmas)
         pred = self.model(noisy, encoder_hidden_states=prompt.to(self.dev, BF16), pooled_projections=pooled.to(self.dev, BF16),
                           timestep=timesteps).sample
-        loss = _MseBf16Chunk.apply(pred, target, self._mse_ws)
+        loss = _FusedMse.apply(pred, target, self._mse_ws, ops.mse_bf16_chunk, BF16)
         return (loss, pred, target) if return_pred else loss
 
     def train_step_device(self, latents, prompt, pooled, noise, timesteps, sigmas, loss_out, gscale=1.0):
@@ -507,41 +504,24 @@ class SD3Recipe:
         when given, draws it on the host instead); mix, forward, bf16 loss + dL/dpred and backward replay a launch plan.
         -> loss (0-dim bf16 device tensor); gradients are in the flat gradient buffer."""
         prompt, pooled = self.stack_embeddings(embeddings)
-        if latents.is_cuda or prompt.is_cuda:
-            raise ValueError("optimize_device stages host batches (the sampler yields CPU tensors)")
+        self._host_batch(latents, prompt)
         B = latents.shape[0]
-        nlat, npr, npo = latents.numel(), prompt.numel(), pooled.numel()
-        cpu_gen = generator if (generator is not None and generator.device.type == "cpu") else None
-        host_noise = cpu_gen is not None
-        (o_lat, o_noise, o_pr, o_po, o_t, o_sig), total = _layout([2 * nlat, 2 * nlat if host_noise else 0, 2 * npr, 2 * npo,
-                                                                   4 * B, 2 * B])
-        st = self._stager = getattr(self, "_stager", None) or _Stager(self.dev)
-        pin = st.begin(total)
-
-        def seg(o, n, dtype):
-            return pin[o:o + n].view(dtype)
-        seg(o_lat, 2 * nlat, BF16).view(latents.shape).copy_(latents)
-        if host_noise:
-            torch.randn(latents.shape, generator=cpu_gen, dtype=BF16, out=seg(o_noise, 2 * nlat, BF16).view(latents.shape))
+        cpu_gen = _cpu_generator(generator)
+        host = self._stager.begin(self._layout(latents.shape, prompt.shape, pooled.shape, host_noise=cpu_gen is not None))
+        host["lat"].copy_(latents)
+        self._host_noise(cpu_gen, host)
         _, t, sig = self.scheduler.sample(B, cpu_gen)                                                            # :182-184
-        seg(o_pr, 2 * npr, BF16).view(prompt.shape).copy_(prompt)
-        seg(o_po, 2 * npo, BF16).view(pooled.shape).copy_(pooled)
-        seg(o_t, 4 * B, torch.float32).copy_(t)
-        seg(o_sig, 2 * B, BF16).copy_(sig)
-        land = st.commit(total)
+        host["prompt"].copy_(prompt)
+        host["pooled"].copy_(pooled)
+        host["t"].copy_(t)
+        host["sig"].copy_(sig)
+        dev = self._stager.commit()
+        noise = self._device_noise(generator, dev)                                                               # :180
+        self.train_step_device(dev["lat"], dev["prompt"], dev["pooled"], noise, dev["t"], dev["sig"], self._loss_out, gscale=gscale)
+        return self._loss_out[0].to(BF16)
 
-        def dseg(o, n, dtype):
-            return land[o:o + n].view(dtype)
-        lat_d = dseg(o_lat, 2 * nlat, BF16).view(latents.shape)
-        if host_noise:
-            noise_d = dseg(o_noise, 2 * nlat, BF16).view(latents.shape)
-        else:
-            noise_d = self._scratch("_noise_buf", lat_d)
-            dev_gen = generator if (generator is not None and generator.device.type == "cuda") else None
-            torch.randn(latents.shape, generator=dev_gen, device=self.dev, dtype=BF16, out=noise_d)              # :180
-        loss_out = self.__dict__.setdefault("_loss_out", torch.zeros(1, dtype=torch.float32, device=self.dev))
-        self.train_step_device(lat_d, dseg(o_pr, 2 * npr, BF16).view(prompt.shape), dseg(o_po, 2 * npo, BF16).view(pooled.shape),
-                               noise_d, dseg(o_t, 4 * B, torch.float32), dseg(o_sig, 2 * B, BF16), loss_out, gscale=gscale)
-        return loss_out[0].to(BF16)
-
-    _scratch = SanaRecipe._scratch
+    @staticmethod
+    def _layout(shape, prompt_shape, pooled_shape, host_noise):
+        B = shape[0]
+        return _Layout([("lat", shape, BF16), ("noise", shape if host_noise else (0,), BF16), ("prompt", prompt_shape, BF16),
+                        ("pooled", pooled_shape, BF16), ("t", (B,), F32), ("sig", (B,), BF16)])
