@@ -475,7 +475,8 @@ uint64_t yat_ln_bwd_workspace_bytes(int M, int D, int rpb) {
 int yat_ln_modulate_bwd(int M, int D, int rpb, const void* x, const float* mean, const float* rstd, const void* scale,
                         int mod_ld, const void* dy, const void* dres, void* dx, float* dshift_acc, float* dscale_acc,
                         int acc_ld, void* workspace, int parts, yat_stream_t stream) {
-    if (M <= 0 || rpb <= 0 || M % rpb || (mod_ld & 7) || !x || !dy || parts < 1 || parts > 3) return YAT_EINVAL;
+    // (D & 7: the column pass loads 8 columns at once and, launched alone with parts = 2, has no dispatch_maxv in front of it)
+    if (M <= 0 || rpb <= 0 || M % rpb || (D & 7) || (mod_ld & 7) || !x || !dy || parts < 1 || parts > 3) return YAT_EINVAL;
     if ((parts & 1) && !dx) return YAT_EINVAL;
     if ((parts & 2) && (!workspace || !dshift_acc || !dscale_acc)) return YAT_EINVAL;
     const int B = M / rpb;
