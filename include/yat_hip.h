@@ -559,6 +559,46 @@ int yat_vae_kl_sample(int B, int HW, int L, int ld, const void* moments, const v
                       float scale, void* out, yat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * Gemma-2 text encoder (transformers Gemma2Model, forward only, bf16): the prompt embeddings of SANA --
+ * pipe.encode_prompt train_sana.py:84-94 (training captions), :113-129 (validation prompts with the complex human
+ * instruction), common/trainer.py:307-308 (the empty prompt).  The text side runs PACKED: prompt b is the row range
+ * [row_offsets[b], row_offsets[b + 1]) of one [rows, .] matrix; no pad row exists (the reference pads on the right and the
+ * model is causal, so a real token never sees a pad).  q_proj|k_proj|v_proj, o_proj, gate_proj|up_proj and down_proj run on
+ * yat_gemm_bf16_ex (yat_amd/gemma2.py); every pointer below is 16-byte aligned unless it holds int32.
+ *
+ * yat_embed_rows: embed_tokens: out[r, :] = bf16(table[ids[r], :] * scale), scale = (float)bf16(sqrt(hidden)).  ids: int32
+ *   [rows] on the device; table: [vocab, D]; D % 8 == 0.  The caller rejects an id outside [0, vocab) before the call; the
+ *   kernel never gathers through one (such a row is written as zeros).
+ * yat_gemma_rmsnorm: Gemma2RMSNorm: y = bf16(x * rsqrt(mean(x^2) + eps) * (1 + w)), all in fp32 with ONE rounding
+ *   (yat_rmsnorm_fwd and yat_dcae_rmsnorm_bias round before the weight).  residual != NULL: y = bf16(residual + y) -- the
+ *   block's post_attention_layernorm / post_feedforward_layernorm followed by the residual add.  x, residual, y: [M, D],
+ *   D % 8 == 0; y may alias residual (not x).
+ * yat_rope_qk: apply_rotary_pos_emb, in place, on the first `heads` (= Hq + Hkv: the q and k blocks) head-sized column blocks
+ *   of the fused projection qkv [rows, ld]:  x' = bf16(bf16(x * cos) + bf16(rotate_half(x) * sin)).  cos_table / sin_table:
+ *   bf16 [max_len, dh] as Gemma2RotaryEmbedding returns them; positions: int32 [rows] on the device, the index of a row inside
+ *   its own prompt (a row whose position is outside [0, max_len) is left as it is).  dh % 16 == 0.  Columns from heads * dh on
+ *   (the v block) are not touched.
+ * yat_geglu: out[m, n] = bf16(bf16(gelu_tanh(gate[m, n])) * up[m, n]) -- Gemma2MLP's act_fn(gate_proj(x)) * up_proj(x) on the
+ *   two column blocks of the fused gate|up projection (row stride ld); out has row stride ldo.  N % 8 == 0.
+ * yat_gemma_attn_fwd: eager_attention_forward of Gemma2Attention over packed prompts: causal, grouped-query (query head h
+ *   reads kv head h / (Hq / Hkv)), s = q k^T * scale, s = softcap * tanh(s / softcap) when softcap > 0, keys j > i dropped,
+ *   softmax and accumulation in fp32 (the probabilities rounded to bf16 for the P V product; the row sum adds the same
+ *   rounded values), out = bf16 [rows, Hq * dh] with row stride ldo.  q, k, v are the column blocks of qkv [rows, ld] that
+ *   start at columns q_off, k_off, v_off (multiples of 8).  row_offsets: int32 [B + 1] on the device, ascending, inside
+ *   [0, rows]; no prompt is longer than max_len.  YAT_EINVAL without a launch: dh != 256, Hq % Hkv != 0, max_len > 1024.
+ * ------------------------------------------------------------------------------------------ */
+int yat_embed_rows(int rows, int D, int vocab, const void* ids, const void* table, float scale, void* out,
+                   yat_stream_t stream);
+int yat_gemma_rmsnorm(int M, int D, float eps, const void* x, const void* w, const void* residual, void* y,
+                      yat_stream_t stream);
+int yat_rope_qk(int rows, int heads, int dh, int max_len, void* qkv, int ld, const void* positions, const void* cos_table,
+                const void* sin_table, yat_stream_t stream);
+int yat_geglu(int M, int N, const void* gate, const void* up, int ld, void* out, int ldo, yat_stream_t stream);
+int yat_gemma_attn_fwd(int B, int rows, int Hq, int Hkv, int dh, int max_len, float scale, float softcap, const void* qkv,
+                       int ld, int q_off, int k_off, int v_off, const void* row_offsets, void* out, int ldo,
+                       yat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * launch plans: replay a recorded sequence of entry-point calls and stream / event operations in ONE call.
  * A training step over the same buffers issues the same ~900 launches and ~500 stream / event operations every time
  * (yat_amd/flat.py records them); replaying the list from C costs ~1 us per entry instead of a host-language call each.

@@ -7,11 +7,16 @@ train_sana.py:221-237), driving the MI355X-native hot path.
 
 ``pretrained_model_path`` (or ``pretrained_pipe_path``/transformer) must be a LOCAL diffusers directory
 (config.json + diffusion_pytorch_model.safetensors); with neither present the 1.6B architecture is random-initialised
-(there is no network here).  Text encoding and the ``extract_features`` / ``compute_features`` loop are outside the hot-path
-scope: training consumes cached-feature shards (``python -m yat_amd.extract_latents`` makes their latents on the HIP DC-AE
-encoder, which ``extract_latents`` also uses); validation samples latents from cached prompt embeddings and, when
-``<pretrained_pipe_path>/vae`` holds the DC-AE, decodes them to images on the HIP decoder (yat_amd/dcae.py).
+(there is no network here).  The ``extract_features`` / ``compute_features`` loop is outside the hot-path scope: training
+consumes cached-feature shards (``python -m yat_amd.extract_latents`` makes their latents on the HIP DC-AE encoder, which
+``extract_latents`` also uses; ``python -m yat_amd.encode_prompts`` makes their prompt embeddings on the HIP Gemma-2 encoder,
+which ``extract_embeddings`` also uses).  With ``<pretrained_pipe_path>/text_encoder`` + ``/tokenizer`` present, CFG dropout
+needs no ``empty_embeds.pt`` and validation no ``validation_embeds.pt``; without them both come from those cached files.
+When ``<pretrained_pipe_path>/vae`` holds the DC-AE, validation decodes its latents to images on the HIP decoder
+(yat_amd/dcae.py).
 """
+import os
+
 from yat_amd import sampler
 from yat_amd.dit_trainer import DiTTrainer, main
 from yat_amd.recipe import SanaRecipe
@@ -24,7 +29,9 @@ class SanaModel(DiTTrainer):
     ``vae.encode(images.to(bf16)).latent.to(bf16) * scaling_factor``.  ``validate`` is :99-161: flow-match Euler sampling,
     generator seeded 42 on the device (:108), entries (prompt_embeds [1,T,C], mask [1,T], negative_embeds, negative_mask);
     the decode on the HIP DC-AE decoder (yat_amd/dcae.py) is :153-157.  ``optimize`` is :163-219 with the trainer's per-step
-    generator (``SanaRecipe``)."""
+    generator (``SanaRecipe``).  ``extract_embeddings`` is :84-94 and the prompt encoding of ``validate`` :113-129 on the HIP
+    Gemma-2 encoder (yat_amd/gemma2.py, yat_amd/encode_prompts.py), built at the first call from
+    ``<pretrained_pipe_path>/text_encoder`` + ``/tokenizer``."""
     model_cls, config_cls, recipe_cls = SanaTransformer2DModelHIP, SanaConfig, SanaRecipe           # train_sana.py:20-23
     recipe_args = {"pad_to": 512}
     vae_compression, vae_noun = 32, "DC-AE"                                                         # :45-57
@@ -32,6 +39,50 @@ class SanaModel(DiTTrainer):
 
     def make_scheduler(self, raw):
         return FlowMatchSchedule(shift=float(raw.get("shift", 3.0)))                                # :41
+
+    def _text_encoder(self):
+        """(encoder, tokenizer), built once; NotImplementedError without the two directories."""
+        from yat_amd.gemma2 import find_text_encoder_dirs
+        enc = getattr(self, "text_encoder", None)
+        if enc is not None and enc[0].layers is not None:
+            return enc
+        pipe = getattr(self.params, "pretrained_pipe_path", None)
+        if find_text_encoder_dirs(pipe) is None:
+            want = os.path.join(pipe or "<pretrained_pipe_path>", "text_encoder")
+            raise NotImplementedError(f"text encoding needs the Gemma-2 encoder in {want!r} (config.json + safetensors) and the "
+                                      "tokenizer beside it; without them, train from cached-feature shards")
+        from yat_amd.encode_prompts import load_encoder
+        enc = load_encoder(pipe, device=self.accelerator.device)
+        want = self.model.config.caption_channels
+        if enc[0].H != want:
+            raise ValueError(f"the text encoder's hidden size {enc[0].H} is not the transformer's caption_channels {want}")
+        print(enc[0].describe())
+        self.text_encoder = enc
+        return enc
+
+    def extract_embeddings(self, captions):
+        from yat_amd.encode_prompts import extract_embeddings
+        encoder, tokenizer = self._text_encoder()
+        return extract_embeddings(encoder, tokenizer, captions,
+                                  max_batch=getattr(self.params, "text_encoder_max_batch_size", None))
+
+    def load_empty_embeddings(self):
+        return [e.cpu() for e in super().load_empty_embeddings()]      # the step stages its embeddings from the host
+
+    def encode_validation_prompts(self):
+        """Encoded once and kept for the later validations; the encoder's weights are freed afterwards (:131)."""
+        kept = getattr(self, "validation_embeds", None)
+        if kept is not None:
+            return kept
+        try:
+            encoder, tokenizer = self._text_encoder()
+        except NotImplementedError:
+            return None
+        from yat_amd.encode_prompts import validation_embeddings
+        self.validation_embeds = validation_embeddings(encoder, tokenizer, list(self.params.validation_prompts or []))
+        encoder.free()
+        self.text_encoder = None
+        return self.validation_embeds
 
     def sample_validation(self, embeds, side, generator):
         pe, pm, ne, nm = embeds

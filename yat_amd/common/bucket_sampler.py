@@ -22,6 +22,7 @@ Out of scope: R2/HTTP download, on-the-fly VAE/text encoding, Dreambooth, dual-G
 """
 from __future__ import annotations
 
+import atexit
 import os
 import queue
 import random
@@ -91,27 +92,34 @@ class BucketSampler:
                 yield from samples
 
     def _prefetched(self, stream):
-        """``stream`` drained by a daemon producer thread through a bounded queue; exceptions travel to the consumer."""
+        """``stream`` drained by a daemon producer thread through a bounded queue; exceptions travel to the consumer.  The
+        thread is stopped AND joined when the consumer is closed, by ``close()`` and, at the latest, by an exit hook: a daemon
+        thread that is still inside a torch call when the interpreter finalises is ended by the interpreter from within C++
+        frames, which aborts the process ("terminate called without an active exception") after the work is done."""
         q = queue.Queue(maxsize=self.decode_ahead)
         stop = threading.Event()
         done = object()
 
+        def put(item):
+            while not stop.is_set():
+                try:
+                    q.put(item, timeout=0.2)
+                    return True
+                except queue.Full:
+                    continue
+            return False
+
         def produce():
             try:
                 for item in stream:
-                    while not stop.is_set():
-                        try:
-                            q.put(item, timeout=0.2)
-                            break
-                        except queue.Full:
-                            continue
-                    if stop.is_set():
+                    if not put(item):
                         return
-                q.put(done)
+                put(done)
             except BaseException as e:      # noqa: BLE001 -- re-raised on the training thread
-                q.put(e)
+                put(e)
         t = threading.Thread(target=produce, name="yat-shard-decode", daemon=True)
         self._producer = (t, stop)
+        atexit.register(self.close)
         t.start()
         try:
             while True:
@@ -122,12 +130,19 @@ class BucketSampler:
                     raise item
                 yield item
         finally:
-            stop.set()
+            self._join(t, stop)
+
+    @staticmethod
+    def _join(t, stop):
+        stop.set()
+        if t is not threading.current_thread():
+            t.join(timeout=10.0)            # (the producer looks at ``stop`` every 0.2 s and after every decoded shard)
 
     def close(self):
-        if self._producer is not None:
-            self._producer[1].set()
-            self._producer = None
+        prod, self._producer = self._producer, None
+        if prod is not None:
+            self._join(*prod)
+            atexit.unregister(self.close)
 
     def process_element(self, elem):
         ratio = float(elem["ratio"])

@@ -301,8 +301,8 @@ class Model:
 
     def load_empty_embeddings(self):
         """The embedding of the empty prompt that whole-batch CFG dropout substitutes (:306-308,319-323).  The reference gets
-        it from ``extract_embeddings([''])`` -- a text-encoder pass, outside this build's scope -- so it is read from the
-        cache like every other feature: ``empty_embeds.pt`` next to the shards (or in the cwd), holding what that call
+        it from ``extract_embeddings([''])`` -- a text-encoder pass, which only SANA with a text encoder in its pipe directory
+        can run here -- so otherwise it is read from the cache like every other feature: ``empty_embeds.pt`` next to the shards (or in the cwd), holding what that call
         returns (SANA / PixArt: a list with one ``[L, C]`` tensor of the mask-true rows, train_sana.py:84-94).  A subclass
         with a text encoder may still override ``extract_embeddings``; it is tried first."""
         try:

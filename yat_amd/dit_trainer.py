@@ -71,19 +71,24 @@ class DiTTrainer(Model):
     def extract_embeddings(self, captions):
         raise NotImplementedError("text encoding is outside the hot-path scope; train from cached-feature shards")
 
+    def encode_validation_prompts(self):
+        """The first third of the reference's ``validate()`` for a trainer that has a text encoder: the entries of
+        ``validation_embeds.pt`` made from ``params.validation_prompts``; None without one."""
+        return None
+
     def validate(self):
         """The middle third of the reference's ``validate()``: 20 sampling steps with CFG 5.0 over the HIP transformer,
-        generator seeded 42.  The text encoders are outside this build's scope, so the prompt embeddings come from a cached
-        file (``validation_embeds.pt`` next to the shards or in the cwd: a list of tuples as ``pipe.encode_prompt`` returns
-        them) and the result is the latents (``output_type='latent'``), stored under models/<step>/ with a three-channel
+        generator seeded 42.  The prompt embeddings come from a cached file (``validation_embeds.pt`` next to the shards or in
+        the cwd: a list of tuples as ``pipe.encode_prompt`` returns them) or, without one, from ``encode_validation_prompts``
+        (SANA with a text encoder in the pipe directory; the other text encoders are outside this build's scope), and the result is the latents (``output_type='latent'``), stored under models/<step>/ with a three-channel
         preview for the logger.  With a VAE in ``<pretrained_pipe_path>/vae`` the last third runs too: each latent is decoded
         on the HIP decoder (built at the first call; ``vae.decode(latent / scaling_factor)`` -> ``postprocess``), logged as
         ``validation/{idx}/{prompt}`` and written to models/<step>/validation_{idx}.png."""
         cands = [os.path.join(os.path.dirname(p), "validation_embeds.pt") for p in (self.params.local_shard_paths or [])]
         path = next((c for c in cands + ["validation_embeds.pt"] if os.path.isfile(c)), None)
-        if path is None:
+        embeds = torch.load(path, map_location="cpu") if path is not None else self.encode_validation_prompts()
+        if embeds is None:
             raise NotImplementedError("no cached validation embeddings (text encoding is outside the hot-path scope)")
-        embeds = torch.load(path, map_location="cpu")
         gen = torch.Generator(device=self.accelerator.device if self.validation_seed_on_device else "cpu").manual_seed(42)
         side = self.model.config.sample_size
         out = [self.sample_validation(e, side, gen).cpu() for e in embeds]

@@ -1,0 +1,162 @@
+"""Prompts -> SANA prompt embeddings on the HIP Gemma-2 encoder (yat_amd/gemma2.py): the text half of the reference's feature
+extraction and validation (train_sana.py:84-94, :113-129, common/trainer.py:307-308).
+
+    python -m yat_amd.encode_prompts --pipe PIPE [--empty OUT.pt] [--validation prompts.txt OUT.pt] [CAPTION.txt ...]
+
+* ``CAPTION.txt ...``: writes ``STEM.emb.pt`` next to each ``STEM.txt``: the unpadded ``[L, C]`` bf16 rows the reference
+  stores (train_sana.py:92-94) -- the sidecar ``python -m yat_amd.extract_latents`` reads;
+* ``--empty OUT.pt``: ``extract_embeddings([""])``, a list with one ``[L, C]`` tensor (the trainer's ``empty_embeds.pt``);
+* ``--validation prompts.txt OUT.pt``: one prompt per line -> the list of ``(prompt_embeds [1, 300, C], mask [1, 300],
+  negative_embeds, negative_mask)`` tuples the trainer's ``validate()`` reads (``validation_embeds.pt``): the prompt with
+  the complex human instruction, the negative prompt ``""`` without it (train_sana.py:113-129).
+
+The tokenizer is ``PIPE/tokenizer/tokenizer.json``, read with the ``tokenizers`` package.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+
+import torch
+
+MAX_SEQUENCE_LENGTH = 300             # SanaPipeline.encode_prompt's max_sequence_length default
+
+# The instruction the reference's validate() puts in front of every validation prompt (train_sana.py:113-122; the text SANA
+# publishes for its pipeline).
+COMPLEX_HUMAN_INSTRUCTION = [
+    "Given a user prompt, generate an 'Enhanced prompt' that provides detailed visual descriptions suitable for image generation. Evaluate the level of detail in the user prompt:",
+    "- If the prompt is simple, focus on adding specifics about colors, shapes, sizes, textures, and spatial relationships to create vivid and concrete scenes.",
+    "- If the prompt is already detailed, refine and enhance the existing details slightly without overcomplicating.",
+    "Here are examples of how to transform or refine prompts:",
+    "- User Prompt: A cat sleeping -> Enhanced: A small, fluffy white cat curled up in a round shape, sleeping peacefully on a warm sunny windowsill, surrounded by pots of blooming red flowers.",
+    "- User Prompt: A busy city street -> Enhanced: A bustling city street scene at dusk, featuring glowing street lamps, a diverse crowd of people in colorful clothing, and a double-decker bus passing by towering glass skyscrapers.",
+    "Please generate only the enhanced description for the prompt below and avoid including any additional commentary or evaluations:",
+    "User Prompt: ",
+]
+
+
+def load_tokenizer(tokenizer_dir: str):
+    """``<tokenizer_dir>/tokenizer.json`` through the ``tokenizers`` package; its own padding / truncation are switched off
+    (``tokenize_prompts`` applies the pipeline's)."""
+    try:
+        from tokenizers import Tokenizer
+    except ImportError as e:
+        raise ImportError("encoding prompts needs the `tokenizers` package (it reads <pipe>/tokenizer/tokenizer.json); without "
+                          "it, train from cached embeddings") from e
+    tok = Tokenizer.from_file(os.path.join(tokenizer_dir, "tokenizer.json"))
+    tok.no_padding()
+    tok.no_truncation()
+    return tok
+
+
+def tokenize_prompts(tokenizer, prompts, complex_human_instruction=None, max_sequence_length=MAX_SEQUENCE_LENGTH):
+    """The prompt rules of diffusers ``SanaPipeline.encode_prompt`` / ``SanaPipeline._get_gemma_prompt_embeds`` [RECALL:
+    restated from knowledge of upstream diffusers, which is not importable here]:
+
+    * ``_text_preprocessing`` without ``clean_caption``: ``text.lower().strip()``;
+    * with a complex human instruction: ``chi = "\\n".join(instruction)``, every prompt becomes ``chi + prompt`` and
+      ``max_length_all = len(tokenizer.encode(chi)) + max_sequence_length - 2``; without: ``max_length_all =
+      max_sequence_length``;
+    * ``tokenizer(prompt, padding="max_length", max_length=max_length_all, truncation=True, add_special_tokens=True)``: the
+      tokenizer's template supplies BOS, the ids are cut at ``max_length_all`` and padded on the right;
+    * after the encoder: ``select_index = [0] + list(range(-max_sequence_length + 1, 0))`` on embeddings and mask
+      (``select_rows``).
+
+    -> (list of id lists without the padding, max_length_all)."""
+    if isinstance(prompts, str):
+        prompts = [prompts]
+    texts = [p.lower().strip() for p in prompts]
+    max_length_all = max_sequence_length
+    if complex_human_instruction:
+        chi = "\n".join(complex_human_instruction)
+        texts = [chi + t for t in texts]
+        max_length_all = len(tokenizer.encode(chi).ids) + max_sequence_length - 2
+    return [list(tokenizer.encode(t).ids)[:max_length_all] for t in texts], max_length_all
+
+
+def select_rows(emb: torch.Tensor, max_length_all: int, max_sequence_length=MAX_SEQUENCE_LENGTH):
+    """``emb``: the ``[L, C]`` rows of one prompt's real tokens -> (``[max_sequence_length, C]``, mask ``[max_sequence_length]``
+    int64): row 0, then the last ``max_sequence_length - 1`` rows of the sequence padded on the right to ``max_length_all``.
+    A pad row comes back as zeros with mask 0 (the reference computes something there that the mask then hides)."""
+    L = emb.shape[0]
+    index = torch.tensor([0] + list(range(max_length_all - max_sequence_length + 1, max_length_all)))
+    real = index < L
+    out = torch.zeros(len(index), emb.shape[1], dtype=emb.dtype, device=emb.device)
+    out[real.to(emb.device)] = emb[index[real].to(emb.device)]
+    return out, real.to(torch.int64)
+
+
+def encode_prompt(encoder, tokenizer, prompts, complex_human_instruction=None, max_batch=None):
+    """``pipe.encode_prompt(prompts, complex_human_instruction=..., do_classifier_free_guidance=False)`` -> (embeds ``[B, 300,
+    C]`` bf16, mask ``[B, 300]`` int64), both on the encoder's device.  ``encoder.encode`` maps id tensors to ``[L, C]`` rows."""
+    ids, max_length_all = tokenize_prompts(tokenizer, prompts, complex_human_instruction)
+    rows = encoder.encode([torch.tensor(i, dtype=torch.int64) for i in ids], max_batch=max_batch)
+    picked = [select_rows(r, max_length_all) for r in rows]
+    return torch.stack([p[0] for p in picked]), torch.stack([p[1] for p in picked]).to(picked[0][0].device)
+
+
+def extract_embeddings(encoder, tokenizer, captions, max_batch=None):
+    """train_sana.py:84-94: ``encode_prompt`` without an instruction, then the mask-true rows of each prompt -- without an
+    instruction those are the rows of its (truncated) tokens, so nothing is padded and selected first."""
+    ids, _ = tokenize_prompts(tokenizer, list(captions))
+    return encoder.encode([torch.tensor(i, dtype=torch.int64) for i in ids], max_batch=max_batch)
+
+
+def validation_embeddings(encoder, tokenizer, prompts):
+    """train_sana.py:124-129: per prompt ``pipe.encode_prompt(prompt, complex_human_instruction=...)`` with classifier-free
+    guidance on and the default negative prompt ``""`` -> a list of (prompt_embeds, mask, negative_embeds, negative_mask)."""
+    out = []
+    neg, neg_mask = encode_prompt(encoder, tokenizer, [""])
+    for p in prompts:
+        pe, pm = encode_prompt(encoder, tokenizer, [p], COMPLEX_HUMAN_INSTRUCTION)
+        out.append((pe.cpu(), pm.cpu(), neg.cpu().clone(), neg_mask.cpu().clone()))
+    return out
+
+
+def load_encoder(pipe_dir: str, device="cuda", softcap=True):
+    """(Gemma2EncoderHIP, tokenizer) of a SANA pipeline directory."""
+    from .gemma2 import Gemma2EncoderHIP, find_text_encoder_dirs
+    dirs = find_text_encoder_dirs(pipe_dir)
+    if dirs is None:
+        raise FileNotFoundError(f"{pipe_dir!r} holds no text_encoder/config.json + tokenizer/tokenizer.json")
+    tokenizer = load_tokenizer(dirs[1])
+    return Gemma2EncoderHIP.from_pretrained(dirs[0], device=device, softcap=softcap), tokenizer
+
+
+def main(argv=None, loader=load_encoder) -> None:
+    ap = argparse.ArgumentParser(prog="python -m yat_amd.encode_prompts",
+                                 description="encode captions / prompts into SANA prompt embeddings on the HIP Gemma-2 encoder")
+    ap.add_argument("--pipe", required=True, help="SANA pipeline directory (text_encoder/ and tokenizer/)")
+    ap.add_argument("--device", default="cuda")
+    ap.add_argument("--no-softcap", action="store_true", help="drop the attention soft cap (what transformers' SDPA path computes)")
+    ap.add_argument("--empty", metavar="OUT.pt", help="write the empty prompt's embedding (empty_embeds.pt)")
+    ap.add_argument("--validation", nargs=2, metavar=("PROMPTS.txt", "OUT.pt"), help="one prompt per line -> validation_embeds.pt")
+    ap.add_argument("--batch", type=int, default=8, help="captions per encoder call")
+    ap.add_argument("captions", nargs="*", help="STEM.txt caption files; STEM.emb.pt is written next to each")
+    a = ap.parse_args(argv)
+    encoder, tokenizer = loader(a.pipe, device=a.device, softcap=not a.no_softcap)
+    if hasattr(encoder, "describe"):
+        print(encoder.describe())
+    if a.captions:
+        texts = []
+        for path in a.captions:
+            with open(path, encoding="utf-8") as f:
+                texts.append(f.read())
+        embs = extract_embeddings(encoder, tokenizer, texts, max_batch=a.batch)
+        for path, emb in zip(a.captions, embs):
+            out = os.path.splitext(path)[0] + ".emb.pt"
+            torch.save(emb.to(torch.bfloat16).cpu().clone(), out)
+            print(f"{out}: {tuple(emb.shape)}")
+    if a.empty:
+        emb = extract_embeddings(encoder, tokenizer, [""])
+        torch.save([e.to(torch.bfloat16).cpu().clone() for e in emb], a.empty)
+        print(f"{a.empty}: {tuple(emb[0].shape)}")
+    if a.validation:
+        with open(a.validation[0], encoding="utf-8") as f:
+            prompts = [line.rstrip("\n") for line in f if line.strip()]
+        torch.save(validation_embeddings(encoder, tokenizer, prompts), a.validation[1])
+        print(f"{a.validation[1]}: {len(prompts)} prompt(s)")
+
+
+if __name__ == "__main__":
+    main()

@@ -9,8 +9,9 @@ PixArt-Sigma, SD3.5).
 Per image: PIL decode to RGB -> bucket = ``find_closest_ratio(height / width)`` over the resolution's aspect table ->
 ``img.resize((tw, th), Image.BILINEAR)`` (what torchvision's ``Resize((th, tw))`` does to a PIL image) -> ToTensor /
 Normalize(0.5, 0.5) / bf16 and the encode on the device (``AutoencoderDCEncoderHIP.encode_uint8``) -> one shard sample
-``{__key__, ratio, latent, emb}``.  The text encoder is not built, so the embedding comes from a sidecar file
-``IMAGE_STEM.emb.pt`` next to the image: the unpadded ``[L, C]`` bf16 rows the reference stores (train_sana.py:92-94); an
+``{__key__, ratio, latent, emb}``.  The embedding comes from a sidecar file ``IMAGE_STEM.emb.pt`` next to the image: the
+unpadded ``[L, C]`` bf16 rows the reference stores (train_sana.py:92-94) -- for SANA, ``python -m yat_amd.encode_prompts``
+writes it from ``IMAGE_STEM.txt`` on the HIP Gemma-2 encoder; the T5 / CLIP encoders of the other recipes are not built; an
 ``IMAGE_STEM.pooled.pt`` beside it, when there is one, becomes the sample's ``pooled`` member (SD3.5's pooled projection).
 
 An AutoencoderKL latent is a sample of the encoder's Gaussian: ``--seed`` seeds the generator of its noise on the device (the
@@ -54,8 +55,8 @@ def sidecar_path(image_path: str) -> str:
 def load_embedding(image_path: str) -> torch.Tensor:
     path = sidecar_path(image_path)
     if not os.path.isfile(path):
-        raise FileNotFoundError(f"no text embedding for {image_path!r}: the sidecar {path!r} is missing (the text encoder is "
-                                "not built; store the unpadded [L, C] bf16 embedding there)")
+        raise FileNotFoundError(f"no text embedding for {image_path!r}: the sidecar {path!r} is missing (store the "
+                                "unpadded [L, C] bf16 embedding there; SANA: `python -m yat_amd.encode_prompts` writes it)")
     emb = torch.load(path, map_location="cpu", weights_only=True)
     if not isinstance(emb, torch.Tensor) or emb.dim() != 2:
         raise ValueError(f"{path!r}: expected an [L, C] tensor")

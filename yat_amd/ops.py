@@ -919,3 +919,62 @@ def vae_kl_sample(moments, noise, out, B, HW, L, ld, scale, shift=None):
                                   float(shift if shift is not None else 0.0), float(scale), _p(out), _stream())
     _l.check(rc, "yat_vae_kl_sample")
     return out
+
+
+# ------------------------------------------------------------------------------- Gemma-2 text encoder (yat_amd/gemma2.py)
+def embed_rows(ids_i32, table, scale, out):
+    """out[r] = bf16(table[ids[r]] * scale) (include/yat_hip.h yat_embed_rows).  ``ids_i32``: int32 [rows] on the device; an
+    id outside [0, vocab) raises here (a host check: one device reduction) and is never gathered."""
+    _chk_bf16(table, out)
+    if ids_i32.dtype != torch.int32 or ids_i32.dim() != 1 or not ids_i32.is_contiguous():
+        raise TypeError("embed_rows wants a contiguous 1-D int32 id tensor")
+    vocab, D = table.shape
+    lo, hi = int(ids_i32.min()), int(ids_i32.max())
+    if lo < 0 or hi >= vocab:
+        raise ValueError(f"token id {lo if lo < 0 else hi} is outside the vocabulary [0, {vocab})")
+    rc = _lib().yat_embed_rows(ids_i32.numel(), D, vocab, _p(ids_i32), _p(table), float(scale), _p(out), _stream())
+    _l.check(rc, "yat_embed_rows")
+    return out
+
+
+def gemma_rmsnorm(x2d, w, y, eps=1e-6, residual=None):
+    """Gemma2RMSNorm, one rounding; with ``residual``: y = bf16(residual + norm(x)) (yat_gemma_rmsnorm); y may be residual."""
+    _chk_bf16(x2d, w, y, residual)
+    M, D = x2d.shape
+    rc = _lib().yat_gemma_rmsnorm(M, D, float(eps), _p(x2d), _p(w), _p(residual), _p(y), _stream())
+    _l.check(rc, "yat_gemma_rmsnorm")
+    return y
+
+
+def rope_qk(qkv2d, heads, dh, pos_i32, cos, sin):
+    """apply_rotary_pos_emb in place on the first ``heads`` head blocks (q then k) of ``qkv2d`` (yat_rope_qk)."""
+    _chk_bf16(qkv2d, cos, sin)
+    if pos_i32.dtype != torch.int32 or pos_i32.numel() != qkv2d.shape[0] or tuple(cos.shape) != tuple(sin.shape) \
+            or cos.shape[1] != dh:
+        raise ValueError("rope_qk: int32 positions, one per row, and [max_len, dh] tables")
+    rc = _lib().yat_rope_qk(qkv2d.shape[0], heads, dh, cos.shape[0], _p(qkv2d), qkv2d.stride(0), _p(pos_i32), _p(cos),
+                            _p(sin), _stream())
+    _l.check(rc, "yat_rope_qk")
+    return qkv2d
+
+
+def geglu(gate_up2d, N, out):
+    """out = bf16(bf16(gelu_tanh(gate)) * up) for gate_up2d = [gate | up] (N columns each) (yat_geglu)."""
+    _chk_bf16(gate_up2d, out)
+    rc = _lib().yat_geglu(gate_up2d.shape[0], N, _p(gate_up2d), _p(gate_up2d[:, N:]), gate_up2d.stride(0), _p(out),
+                          out.stride(0), _stream())
+    _l.check(rc, "yat_geglu")
+    return out
+
+
+def gemma_attn_fwd(qkv2d, row_offsets_i32, B, Hq, Hkv, dh, max_len, scale, softcap, out):
+    """Causal grouped-query soft-capped attention over packed prompts (yat_gemma_attn_fwd); qkv2d = [q | k | v] blocks,
+    ``row_offsets_i32``: int32 [B + 1] on the device, ``max_len`` >= the longest prompt, ``softcap`` 0 = none."""
+    _chk_bf16(qkv2d, out)
+    if row_offsets_i32.dtype != torch.int32 or row_offsets_i32.numel() != B + 1:
+        raise ValueError("gemma_attn_fwd: row_offsets must be int32 [B + 1]")
+    rc = _lib().yat_gemma_attn_fwd(B, qkv2d.shape[0], Hq, Hkv, dh, int(max_len), float(scale), float(softcap or 0.0),
+                                   _p(qkv2d), qkv2d.stride(0), 0, Hq * dh, (Hq + Hkv) * dh, _p(row_offsets_i32), _p(out),
+                                   out.stride(0), _stream())
+    _l.check(rc, "yat_gemma_attn_fwd")
+    return out

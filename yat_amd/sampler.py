@@ -8,7 +8,7 @@ What it restates [RECALL, diffusers SanaPipeline.__call__ / FlowMatchEulerDiscre
 * initial latents: N(0,1) in the model dtype from the given generator (init_noise_sigma = 1);
 * per step: the latents are duplicated (unconditional | conditional), one transformer call with the timestep expanded
   to the batch, ``v = v_u + g (v_c - v_u)``, Euler update ``x <- x + (sigma_next - sigma) v`` in fp32, cast back.
-Text encoding (Gemma) and VAE decoding are outside the hot-path scope: the caller passes prompt embeddings and gets
+Text encoding (yat_amd/gemma2.py) and VAE decoding (yat_amd/dcae.py) are the caller's: it passes prompt embeddings and gets
 latents back, exactly the middle third of the reference's validate().
 """
 from __future__ import annotations
