@@ -71,6 +71,47 @@ def test_bad_arguments_are_rejected_without_a_gpu(built_lib):
     assert lib.yat_ln_modulate_fwd(4, 7, 4, 1e-6, 1, 1, 1, 8, 1, 1, 1, None) == -1     # D % 8 != 0
 
 
+def test_linear_attn_bad_arguments_are_rejected_without_a_gpu(built_lib):
+    """yat_linear_attn_fwd / _bwd: la_check and the stride / null checks return YAT_EINVAL before the first launch (csrc/
+    linear_attn.hip), so the fake non-null pointers are never dereferenced and no GPU is needed."""
+    lib = ylib.load()
+    P, EINVAL = 0x7f0000001000, -1
+    good = dict(B=2, N=40, H=3, qkv=P, ld=288, k_off=96, v_off=192, out=P, ld_out=96, dout=P, ld_dout=96, dqkv=P, ld_dqkv=288,
+                state=None, workspace=P)
+
+    def fwd(**kw):
+        a = {**good, **kw}
+        return lib.yat_linear_attn_fwd(a["B"], a["N"], a["H"], a["qkv"], a["ld"], a["k_off"], a["v_off"], a["out"], a["ld_out"],
+                                       a["workspace"], None)
+
+    def bwd(**kw):
+        a = {**good, **kw}
+        return lib.yat_linear_attn_bwd(a["B"], a["N"], a["H"], a["qkv"], a["ld"], a["k_off"], a["v_off"], a["dout"], a["ld_dout"],
+                                       a["dqkv"], a["ld_dqkv"], a["state"], a["workspace"], None)
+
+    for dim in ("B", "N", "H"):
+        for bad in (0, -1):
+            assert fwd(**{dim: bad}) == EINVAL and bwd(**{dim: bad}) == EINVAL, (dim, bad)
+    for name in ("ld", "k_off", "v_off"):                                   # every stride and offset a multiple of 8 elements
+        for bad in (good[name] + 4, good[name] + 1):
+            assert fwd(**{name: bad}) == EINVAL and bwd(**{name: bad}) == EINVAL, (name, bad)
+    assert fwd(ld_out=100) == EINVAL and fwd(ld_out=97) == EINVAL
+    for name in ("ld_dout", "ld_dqkv"):
+        assert bwd(**{name: good[name] + 4}) == EINVAL and bwd(**{name: good[name] + 1}) == EINVAL, name
+    # B * N * ld * 2 bytes must fit the 31-bit byte offsets of the buffer loads: 2^31 - 1 is the last size accepted
+    big = dict(B=8, N=1 << 17, ld=1024)                                     # 2^31 bytes
+    assert fwd(**big) == EINVAL and bwd(**big) == EINVAL
+    assert fwd(B=1, N=(1 << 20) + 1, ld=1024) == EINVAL                     # 2^31 + 2048
+    assert fwd(B=1 << 12, N=1 << 12, ld=1 << 12) == EINVAL                  # 2^37: not a product taken in 32 bits
+    huge = dict(B=1 << 30, N=1 << 30, ld=1 << 30)                           # 2^91: nor one that wraps to 0 in 64 bits
+    assert fwd(**huge) == EINVAL and bwd(**huge) == EINVAL
+    assert fwd(ld=-288) == EINVAL and bwd(ld=-288) == EINVAL
+    for name in ("qkv", "out", "workspace"):
+        assert fwd(**{name: None}) == EINVAL, name
+    for name in ("qkv", "dout", "dqkv", "workspace"):
+        assert bwd(**{name: None}) == EINVAL, name
+
+
 def test_no_kernel_uses_scratch(built_lib):
     """Compiler remarks collected by the build (yat_amd/build/resources.json): no kernel of the library may spill VGPRs
     or touch scratch memory -- on this path a spill in a shared epilogue costs ~10 % of the step and no error."""

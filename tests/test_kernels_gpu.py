@@ -15,6 +15,7 @@ relative error of ~1.1e-3).  Two kinds of check:
 Integer outputs (mask, kv_len) and the optimizer are checked bit-exactly.
 All checks of a test are evaluated and printed before the test fails.
 The row and strip kernels (csrc/rowops.hip, yat_transpose_bf16): dispatch classes and ragged edges in test_rowops_gpu.py.
+Linear attention (csrc/linear_attn.hip): token classes, grid totals, strides, dead rows and hidden state in test_linear_attn_gpu.py.
 """
 import math
 

@@ -494,6 +494,7 @@ uint64_t yat_linear_attn_workspace_bytes(int B, int N, int H) {
 
 static int la_check(int B, int N, int H, int ld, int k_off, int v_off) {
     if (B <= 0 || N <= 0 || H <= 0 || (ld & 7) || (k_off & 7) || (v_off & 7)) return YAT_EINVAL;
+    if (ld < 0 || (uint64_t)B * N > 0x7fffffffull) return YAT_EINVAL;          // (keeps the product below inside 64 bits)
     if ((uint64_t)B * N * ld * 2 > 0x7fffffffull) return YAT_EINVAL;
     return YAT_OK;
 }
