@@ -673,11 +673,19 @@ def _glu_ref(z, wdw, bdw, B, h, w, Hc):
     return y.permute(0, 2, 3, 1).reshape(B * h * w, Hc)
 
 
-# the last two cases take the direct (non-tiled) kernels: w > 64, and a channel count that is not a multiple of 8
+# 3 x 70 x 8 and 6 x 5 x 12 take the direct (non-tiled) kernels: w > 64, and a channel count that is not a multiple of 8
 # (the streaming forward takes the shapes whose rows fill its 16 run slots: 5x9, 32x32, 7x20, 9x16, 10x8, 31x30)
+# Every launcher shrinks bpb (bands per workgroup) until the grid has 3 * 256 * WPS workgroups (forward, pass 1) or 4 * 512
+# (pass 2), so at the small shapes above bpb is always 1.  The last two cases are the smallest at which a workgroup of each
+# band kernel walks several bands (the re-staging barrier of its band loop) and ends on a ragged one, from the launchers'
+# own arithmetic (R rows per band, nbands, bpb):
+#   9 x 34 x 4 x 8192 (40 MB): forward 64ch/3wg (the stream kernel declines w <= 4) R 16, 3 bands, bpb 2; pass 1 (32ch/3wg)
+#     R 16, 3 bands, bpb 3; pass 2 global-z (w < 16) R 16, 3 bands, bpb 3; last band 2 rows of 16
+#   8 x 9 x 50 x 4096 (59 MB): forward 64ch/2wg (w > 48) R 2, 5 bands, bpb 2; pass 2 band kernel R 4, 3 bands, bpb 3; last
+#     band 1 row; the last column segment 2 columns of 8
 @pytest.mark.parametrize("B,h,w,Hc", [(2, 4, 4, 16), (2, 5, 9, 40), (1, 16, 64, 160), (2, 33, 3, 8), (2, 32, 32, 72),
                                       (1, 3, 70, 8), (1, 6, 5, 12), (1, 7, 20, 40), (2, 9, 16, 64), (1, 10, 8, 24),
-                                      (3, 31, 30, 136)])
+                                      (3, 31, 30, 136), (9, 34, 4, 8192), (8, 9, 50, 4096)])
 def test_dwconv_glu_fwd_bwd(ops, B, h, w, Hc):
     M = B * h * w
     z = rnd(M, 2 * Hc, seed=37)

@@ -88,7 +88,7 @@ def _asm_loops(body):
 
 
 def check_dwconv_stream_asm(asm_path: str) -> None:
-    """csrc/dwconv_tile_fwd.inc, dwglu_stream_kernel<SSEG>: the LDS-DMA prefetch of the next rows is awaited with ``s_waitcnt
+    """csrc/dwconv_tile.hpp, dwglu_stream_kernel<SSEG, TCH, WPS>: the LDS-DMA prefetch of the next rows is awaited with ``s_waitcnt
     vmcnt(3*SSEG)`` -- correct only while every wave issues EXACTLY 3*SSEG vector-memory operations (the u / y stores) after
     the prefetch in every step.  A compiler that spills, splits or merges a store, or adds any other vector-memory
     operation to the loop would make the wait return early and the kernel read stale ring rows without any test on this
