@@ -599,6 +599,38 @@ int yat_gemma_attn_fwd(int B, int rows, int Hq, int Hkv, int dh, int max_len, fl
                        yat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * T5 v1.1 text encoder (transformers T5EncoderModel, forward only, bf16): the prompt embeddings of PixArt-Sigma --
+ * pipe.encode_prompt train_pixart_sigma.py:68-74 (training captions), :97-108 (validation prompts).  Packed as the Gemma-2
+ * block above: prompt b is the row range [row_offsets[b], row_offsets[b + 1]) and no pad row exists (the reference pads on the
+ * right and masks the pad keys for every real query; the position bias depends on the distance only, so the real rows of a
+ * padded batch equal the prompt encoded alone).  q|k|v, o, wi_0|wi_1 and wo run on yat_gemm_bf16_ex, the gather on
+ * yat_embed_rows with scale 1 (T5 does not scale its embedding) and the gated GELU on yat_geglu (yat_amd/t5.py).  Every pointer
+ * below is 16-byte aligned unless it holds int32 (bias_rel: 2-byte).
+ * Stated deviation: the module's NewGELUActivation evaluates the tanh formula as about eight separately rounded bf16 ops;
+ *   yat_geglu evaluates it in fp32 and rounds the activation once, so it is no further from the fp32 value (the tests hold the
+ *   encoder to the fp32 truth, not to the bits of the bf16 module).
+ *
+ * yat_t5_rmsnorm: T5LayerNorm in a bf16 module: y = bf16(w * bf16(x * rsqrt(mean(x^2) + eps))), mean and rsqrt in fp32, TWO
+ *   roundings; no mean subtraction, no bias, no 1 + w.  residual != NULL: the block's residual add comes first --
+ *   sum_out = bf16(residual + x) is stored and y is the norm of that stored sum (T5's pre-norm order h = h + sublayer(norm(h)),
+ *   then the next norm reads h: one pass does both).  x, residual, sum_out, y: [M, D], D % 8 == 0; sum_out may alias residual
+ *   (not x, not y) and is not touched when residual == NULL.
+ * yat_t5_attn_fwd: T5Attention of an encoder block over packed prompts: bidirectional, NO 1/sqrt(dh),
+ *   s[i, j] = q_i . k_j + bias_rel[h, (j - i) + (max_len - 1)], every key of the same prompt visible to every query of that
+ *   prompt and no key of another, softmax and accumulation in fp32 (the probabilities rounded to bf16 for the P V product; the
+ *   row sum adds the same rounded values), out = bf16 [rows, H * dh] with row stride ldo.  q, k, v are the column blocks of
+ *   qkv [rows, ld] that start at columns q_off, k_off, v_off.  bias_rel: bf16 [H, 2 * max_len - 1], the learned
+ *   relative-position bias already looked up per distance on the host (yat_amd/t5.py relative_bias_table): the kernel does no
+ *   logarithm and no bucket arithmetic.  row_offsets: int32 [B + 1] on the device, ascending, inside [0, rows]; no prompt is
+ *   longer than max_len.  YAT_EINVAL without a launch: dh != 64, max_len > 512, H < 1, an offset or stride that is not a
+ *   multiple of 8.
+ * ------------------------------------------------------------------------------------------ */
+int yat_t5_rmsnorm(int M, int D, float eps, const void* x, const void* w, const void* residual, void* sum_out, void* y,
+                   yat_stream_t stream);
+int yat_t5_attn_fwd(int B, int rows, int H, int dh, int max_len, const void* qkv, int ld, int q_off, int k_off, int v_off,
+                    const void* bias_rel, const void* row_offsets, void* out, int ldo, yat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * launch plans: replay a recorded sequence of entry-point calls and stream / event operations in ONE call.
  * A training step over the same buffers issues the same ~900 launches and ~500 stream / event operations every time
  * (yat_amd/flat.py records them); replaying the list from C costs ~1 us per entry instead of a host-language call each.

@@ -6,11 +6,13 @@ train_pixart_sigma.py:187-198), driving the MI355X-native path (BASELINE config 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train_pixart_sigma.py --config config.yaml
 
 ``pretrained_model_path`` (or ``pretrained_pipe_path``/transformer) must be a LOCAL diffusers directory; with neither the
-PixArt-Sigma-XL-2 architecture is random-initialised (no network here).  T5 text encoding and the ``extract_features`` loop
-are outside the hot-path scope: training consumes cached-feature shards (``python -m yat_amd.extract_latents`` makes their
-latents on the HIP AutoencoderKL encoder, which ``extract_latents`` also uses); validation samples latents from cached prompt
-embeddings and, when ``<pretrained_pipe_path>/vae`` holds the AutoencoderKL, decodes them to images on the HIP decoder
-(yat_amd/autoencoder_kl.py).
+PixArt-Sigma-XL-2 architecture is random-initialised (no network here).  The ``extract_features`` loop is outside the
+hot-path scope: training consumes cached-feature shards (``python -m yat_amd.extract_latents`` makes their latents on the HIP
+AutoencoderKL encoder, which ``extract_latents`` also uses; ``python -m yat_amd.encode_prompts`` makes their prompt embeddings
+on the HIP T5 encoder, which ``extract_embeddings`` also uses).  With ``<pretrained_pipe_path>/text_encoder`` + ``/tokenizer``
+present, CFG dropout needs no ``empty_embeds.pt`` and validation no ``validation_embeds.pt``; without them both come from
+those cached files.  When ``<pretrained_pipe_path>/vae`` holds the AutoencoderKL, validation decodes its latents to images on
+the HIP decoder (yat_amd/autoencoder_kl.py).
 
 Reference quirk: ``PixartSigmaTrainer.optimize(self, latents, embeddings)`` (:151) still has the two-argument signature
 while ``Model.run`` calls ``optimize(ratio, latents, embeddings, repa_features, generator)`` (common/trainer.py:337) -- at
@@ -31,10 +33,13 @@ class PixartSigmaTrainer(DiTTrainer):
     pipeline's ``**kwargs`` and is ignored), generator seeded 42 on the device (:94), entries (prompt_embeds [1,T,C], mask
     [1,T], negative_embeds, negative_mask) (:100-108); the decode is :137-144.  ``optimize`` is :151-185 (``PixArtRecipe``):
     the reference draws noise and timesteps from the GLOBAL RNGs (:170,172) and ignores the trainer's per-step generator; so
-    does this."""
+    does this.  ``extract_embeddings`` is :68-74 and the prompt encoding of ``validate`` :97-108 on the HIP T5 encoder
+    (yat_amd/t5.py, yat_amd/encode_prompts.py), built at the first call from ``<pretrained_pipe_path>/text_encoder`` +
+    ``/tokenizer``."""
     model_cls, config_cls, recipe_cls = PixArtTransformer2DModelHIP, PixArtConfig, PixArtRecipe     # :24-33
     recipe_args = {"pad_to": 300}
     vae_compression, apply_shift = 8, False                                                         # :41-50
+    text_encoder_kind, text_encoder_noun = "t5", "T5"                                               # :68-74, :97-108
 
     def __init__(self, params, accelerator=None, config: PixArtConfig | None = None):
         if getattr(params, "use_repa", False):
@@ -55,4 +60,5 @@ class PixartSigmaTrainer(DiTTrainer):
 
 
 if __name__ == "__main__":
-    main(PixartSigmaTrainer, "extract_features (VAE/text-encoder feature extraction) is outside this build's scope")
+    main(PixartSigmaTrainer, "extract_features needs the R2 transport, which is outside this build's scope; `python -m "
+                             "yat_amd.extract_latents` and `python -m yat_amd.encode_prompts` make the cached features")

@@ -15,8 +15,6 @@ needs no ``empty_embeds.pt`` and validation no ``validation_embeds.pt``; without
 When ``<pretrained_pipe_path>/vae`` holds the DC-AE, validation decodes its latents to images on the HIP decoder
 (yat_amd/dcae.py).
 """
-import os
-
 from yat_amd import sampler
 from yat_amd.dit_trainer import DiTTrainer, main
 from yat_amd.recipe import SanaRecipe
@@ -36,53 +34,10 @@ class SanaModel(DiTTrainer):
     recipe_args = {"pad_to": 512}
     vae_compression, vae_noun = 32, "DC-AE"                                                         # :45-57
     step_generator = True
+    text_encoder_kind, text_encoder_noun = "gemma2", "Gemma-2"                                      # :84-94, :113-131
 
     def make_scheduler(self, raw):
         return FlowMatchSchedule(shift=float(raw.get("shift", 3.0)))                                # :41
-
-    def _text_encoder(self):
-        """(encoder, tokenizer), built once; NotImplementedError without the two directories."""
-        from yat_amd.gemma2 import find_text_encoder_dirs
-        enc = getattr(self, "text_encoder", None)
-        if enc is not None and enc[0].layers is not None:
-            return enc
-        pipe = getattr(self.params, "pretrained_pipe_path", None)
-        if find_text_encoder_dirs(pipe) is None:
-            want = os.path.join(pipe or "<pretrained_pipe_path>", "text_encoder")
-            raise NotImplementedError(f"text encoding needs the Gemma-2 encoder in {want!r} (config.json + safetensors) and the "
-                                      "tokenizer beside it; without them, train from cached-feature shards")
-        from yat_amd.encode_prompts import load_encoder
-        enc = load_encoder(pipe, device=self.accelerator.device)
-        want = self.model.config.caption_channels
-        if enc[0].H != want:
-            raise ValueError(f"the text encoder's hidden size {enc[0].H} is not the transformer's caption_channels {want}")
-        print(enc[0].describe())
-        self.text_encoder = enc
-        return enc
-
-    def extract_embeddings(self, captions):
-        from yat_amd.encode_prompts import extract_embeddings
-        encoder, tokenizer = self._text_encoder()
-        return extract_embeddings(encoder, tokenizer, captions,
-                                  max_batch=getattr(self.params, "text_encoder_max_batch_size", None))
-
-    def load_empty_embeddings(self):
-        return [e.cpu() for e in super().load_empty_embeddings()]      # the step stages its embeddings from the host
-
-    def encode_validation_prompts(self):
-        """Encoded once and kept for the later validations; the encoder's weights are freed afterwards (:131)."""
-        kept = getattr(self, "validation_embeds", None)
-        if kept is not None:
-            return kept
-        try:
-            encoder, tokenizer = self._text_encoder()
-        except NotImplementedError:
-            return None
-        from yat_amd.encode_prompts import validation_embeddings
-        self.validation_embeds = validation_embeddings(encoder, tokenizer, list(self.params.validation_prompts or []))
-        encoder.free()
-        self.text_encoder = None
-        return self.validation_embeds
 
     def sample_validation(self, embeds, side, generator):
         pe, pm, ne, nm = embeds

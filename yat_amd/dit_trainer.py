@@ -23,6 +23,8 @@ class DiTTrainer(Model):
     apply_shift = None              # ``encode(images, apply_shift=...)``; None: the encoder takes no such argument (DC-AE)
     validation_seed_on_device = True
     step_generator = False          # hand the trainer's per-step generator to the recipe (else: the global RNG streams)
+    text_encoder_kind = None        # "gemma2" / "t5": the pipe's text encoder, built at first use (yat_amd/encode_prompts.py);
+    text_encoder_noun = None        # None: this trainer has no text side and trains from cached embeddings only
 
     def __init__(self, params: TrainingParameters, accelerator=None, config=None):
         super().__init__(params, accelerator)
@@ -68,19 +70,62 @@ class DiTTrainer(Model):
             return self.vae_encoder.encode(images)
         return self.vae_encoder.encode(images, apply_shift=self.apply_shift)
 
+    def _text_encoder(self):
+        """(encoder, tokenizer), built once from ``<pretrained_pipe_path>/text_encoder`` + ``/tokenizer``;
+        NotImplementedError without the two directories (raised before the model or the device is looked at)."""
+        if self.text_encoder_kind is None:
+            raise NotImplementedError("text encoding is outside the hot-path scope; train from cached-feature shards")
+        from .encode_prompts import find_text_dirs, load_encoder
+        enc = getattr(self, "text_encoder", None)
+        if enc is not None and enc[0].layers is not None:
+            return enc
+        pipe = getattr(self.params, "pretrained_pipe_path", None)
+        if find_text_dirs(pipe, self.text_encoder_kind) is None:
+            want = os.path.join(pipe or "<pretrained_pipe_path>", "text_encoder")
+            raise NotImplementedError(f"text encoding needs the {self.text_encoder_noun} encoder in {want!r} (config.json + "
+                                      "safetensors) and the tokenizer beside it; without them, train from cached-feature shards")
+        enc = load_encoder(pipe, device=self.accelerator.device)
+        want = self.model.config.caption_channels
+        if enc[0].H != want:
+            raise ValueError(f"the text encoder's hidden size {enc[0].H} is not the transformer's caption_channels {want}")
+        print(enc[0].describe())
+        self.text_encoder = enc
+        return enc
+
     def extract_embeddings(self, captions):
-        raise NotImplementedError("text encoding is outside the hot-path scope; train from cached-feature shards")
+        from .encode_prompts import rules_for
+        encoder, tokenizer = self._text_encoder()
+        return rules_for(encoder)[0](encoder, tokenizer, captions,
+                                     max_batch=getattr(self.params, "text_encoder_max_batch_size", None))
+
+    def load_empty_embeddings(self):
+        emb = super().load_empty_embeddings()
+        if self.text_encoder_kind is None:
+            return emb
+        return [e.cpu() for e in emb]                                  # the step stages its embeddings from the host
 
     def encode_validation_prompts(self):
         """The first third of the reference's ``validate()`` for a trainer that has a text encoder: the entries of
-        ``validation_embeds.pt`` made from ``params.validation_prompts``; None without one."""
-        return None
+        ``validation_embeds.pt`` made from ``params.validation_prompts``, encoded once and kept for the later validations;
+        the encoder's weights are freed afterwards.  None without a text encoder."""
+        kept = getattr(self, "validation_embeds", None)
+        if kept is not None:
+            return kept
+        try:
+            encoder, tokenizer = self._text_encoder()
+        except NotImplementedError:
+            return None
+        from .encode_prompts import rules_for
+        self.validation_embeds = rules_for(encoder)[1](encoder, tokenizer, list(self.params.validation_prompts or []))
+        encoder.free()
+        self.text_encoder = None
+        return self.validation_embeds
 
     def validate(self):
         """The middle third of the reference's ``validate()``: 20 sampling steps with CFG 5.0 over the HIP transformer,
         generator seeded 42.  The prompt embeddings come from a cached file (``validation_embeds.pt`` next to the shards or in
         the cwd: a list of tuples as ``pipe.encode_prompt`` returns them) or, without one, from ``encode_validation_prompts``
-        (SANA with a text encoder in the pipe directory; the other text encoders are outside this build's scope), and the result is the latents (``output_type='latent'``), stored under models/<step>/ with a three-channel
+        (SANA and PixArt-Sigma with a text encoder in the pipe directory; SD3.5's text encoders are outside this build's scope), and the result is the latents (``output_type='latent'``), stored under models/<step>/ with a three-channel
         preview for the logger.  With a VAE in ``<pretrained_pipe_path>/vae`` the last third runs too: each latent is decoded
         on the HIP decoder (built at the first call; ``vae.decode(latent / scaling_factor)`` -> ``postprocess``), logged as
         ``validation/{idx}/{prompt}`` and written to models/<step>/validation_{idx}.png."""

@@ -1,5 +1,7 @@
-"""Prompts -> SANA prompt embeddings on the HIP Gemma-2 encoder (yat_amd/gemma2.py): the text half of the reference's feature
-extraction and validation (train_sana.py:84-94, :113-129, common/trainer.py:307-308).
+"""Prompts -> prompt embeddings on the HIP text encoders: SANA's Gemma-2 (yat_amd/gemma2.py; train_sana.py:84-94, :113-129,
+common/trainer.py:307-308) and PixArt-Sigma's T5 v1.1 (yat_amd/t5.py; train_pixart_sigma.py:68-74, :97-108), the text half of the
+reference's feature extraction and validation.  ``PIPE/text_encoder/config.json``'s ``model_type`` (``gemma2`` or ``t5``) picks
+the encoder and its prompt rules.
 
     python -m yat_amd.encode_prompts --pipe PIPE [--empty OUT.pt] [--validation prompts.txt OUT.pt] [CAPTION.txt ...]
 
@@ -8,13 +10,15 @@ extraction and validation (train_sana.py:84-94, :113-129, common/trainer.py:307-
 * ``--empty OUT.pt``: ``extract_embeddings([""])``, a list with one ``[L, C]`` tensor (the trainer's ``empty_embeds.pt``);
 * ``--validation prompts.txt OUT.pt``: one prompt per line -> the list of ``(prompt_embeds [1, 300, C], mask [1, 300],
   negative_embeds, negative_mask)`` tuples the trainer's ``validate()`` reads (``validation_embeds.pt``): the prompt with
-  the complex human instruction, the negative prompt ``""`` without it (train_sana.py:113-129).
+  the complex human instruction, the negative prompt ``""`` without it (train_sana.py:113-129); a T5 pipe has no instruction.
 
-The tokenizer is ``PIPE/tokenizer/tokenizer.json``, read with the ``tokenizers`` package.
+The tokenizer is ``PIPE/tokenizer/tokenizer.json``, read with the ``tokenizers`` package; a T5 pipe that ships only
+``PIPE/tokenizer/spiece.model`` (PixArt-Sigma does) is read with ``sentencepiece``.
 """
 from __future__ import annotations
 
 import argparse
+import json
 import os
 
 import torch
@@ -113,8 +117,134 @@ def validation_embeddings(encoder, tokenizer, prompts):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ T5 (PixArt-Sigma) rules
+class T5Tokenizer:
+    """T5's tokenizer rule over a sentencepiece model: ``tokenize(text, max_length)`` = the pieces cut to ``max_length - 1``,
+    then EOS (the id of ``</s>``) -- what ``transformers.T5Tokenizer(text, max_length=..., truncation=True,
+    add_special_tokens=True)`` returns before its padding.  The empty text is ``[eos]``."""
+
+    def __init__(self, pieces, eos_id: int):
+        self._pieces, self.eos_id = pieces, int(eos_id)
+
+    def tokenize(self, text: str, max_length: int = MAX_SEQUENCE_LENGTH):
+        return [int(i) for i in self._pieces(text)][:max_length - 1] + [self.eos_id]
+
+
+def load_t5_tokenizer(tokenizer_dir: str) -> T5Tokenizer:
+    """``<tokenizer_dir>/tokenizer.json`` through ``tokenizers`` when present (encoded without special tokens; EOS is appended
+    here), else ``<tokenizer_dir>/spiece.model`` through ``sentencepiece``."""
+    fast = os.path.join(tokenizer_dir, "tokenizer.json")
+    if os.path.isfile(fast):
+        try:
+            from tokenizers import Tokenizer
+        except ImportError as e:
+            raise ImportError("encoding prompts needs the `tokenizers` package (it reads <pipe>/tokenizer/tokenizer.json); "
+                              "without it, train from cached embeddings") from e
+        tok = Tokenizer.from_file(fast)
+        tok.no_padding()
+        tok.no_truncation()
+        eos = tok.token_to_id("</s>")
+        if eos is None:
+            raise ValueError(f"{fast}: no </s> token")
+        return T5Tokenizer(lambda text: tok.encode(text, add_special_tokens=False).ids, eos)
+    try:
+        import sentencepiece
+    except ImportError as e:
+        raise ImportError("encoding prompts needs the `sentencepiece` package (it reads <pipe>/tokenizer/spiece.model); "
+                          "without it, train from cached embeddings") from e
+    sp = sentencepiece.SentencePieceProcessor(model_file=os.path.join(tokenizer_dir, "spiece.model"))
+    eos = sp.piece_to_id("</s>")
+    if eos == sp.unk_id():
+        raise ValueError(f"{tokenizer_dir}/spiece.model: no </s> piece")
+    return T5Tokenizer(lambda text: sp.encode(text), eos)
+
+
+def tokenize_prompts_t5(tokenizer: T5Tokenizer, prompts, max_sequence_length=MAX_SEQUENCE_LENGTH):
+    """The prompt rules of diffusers ``PixArtSigmaPipeline.encode_prompt`` [RECALL: restated from knowledge of upstream
+    diffusers, which is not importable here]:
+
+    * ``_text_preprocessing`` without ``clean_caption``: ``text.lower().strip()``;
+    * ``max_sequence_length = 300``;
+    * ``tokenizer(text, padding="max_length", max_length=300, truncation=True, add_special_tokens=True)``: the pieces are cut
+      to 299 and ``</s>`` closes them, then the ids are padded on the right with 0;
+    * the encoder runs under the attention mask; with classifier-free guidance the negative prompt ``""`` is padded to the
+      same 300.
+
+    -> list of id lists without the padding (the empty prompt is ``[eos]``)."""
+    if isinstance(prompts, str):
+        prompts = [prompts]
+    return [tokenizer.tokenize(p.lower().strip(), max_sequence_length) for p in prompts]
+
+
+def extract_embeddings_t5(encoder, tokenizer, captions, max_batch=None):
+    """train_pixart_sigma.py:68-74: ``encode_prompt`` then the mask-true rows of each prompt -- the rows of its real tokens,
+    so nothing is padded first."""
+    ids = tokenize_prompts_t5(tokenizer, list(captions))
+    return encoder.encode([torch.tensor(i, dtype=torch.int64) for i in ids], max_batch=max_batch)
+
+
+def encode_prompt_t5(encoder, tokenizer, prompts, max_batch=None, max_sequence_length=MAX_SEQUENCE_LENGTH):
+    """``pipe.encode_prompt(prompts, do_classifier_free_guidance=False)`` -> (embeds ``[B, 300, C]`` bf16, mask ``[B, 300]``
+    int64), both on the encoder's device.  A pad row comes back as zeros with mask 0 (the reference computes something there
+    that the mask then hides)."""
+    rows = extract_embeddings_t5(encoder, tokenizer, [prompts] if isinstance(prompts, str) else prompts, max_batch)
+    emb = torch.zeros(len(rows), max_sequence_length, rows[0].shape[1], dtype=rows[0].dtype, device=rows[0].device)
+    mask = torch.zeros(len(rows), max_sequence_length, dtype=torch.int64, device=rows[0].device)
+    for b, r in enumerate(rows):
+        emb[b, :r.shape[0]], mask[b, :r.shape[0]] = r, 1
+    return emb, mask
+
+
+def validation_embeddings_t5(encoder, tokenizer, prompts):
+    """train_pixart_sigma.py:97-108: per prompt ``pipe.encode_prompt(prompt)`` with classifier-free guidance on and the
+    default negative prompt ``""`` -> a list of (prompt_embeds, mask, negative_embeds, negative_mask) on the CPU.  PixArt has no
+    complex human instruction."""
+    out = []
+    neg, neg_mask = encode_prompt_t5(encoder, tokenizer, [""])
+    for p in prompts:
+        pe, pm = encode_prompt_t5(encoder, tokenizer, [p])
+        out.append((pe.cpu(), pm.cpu(), neg.cpu().clone(), neg_mask.cpu().clone()))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------- dispatch
+def rules_for(encoder):
+    """(extract_embeddings, validation_embeddings) for an encoder, by its ``model_type`` (absent: Gemma-2's)."""
+    if getattr(encoder, "model_type", "gemma2") == "t5":
+        return extract_embeddings_t5, validation_embeddings_t5
+    return extract_embeddings, validation_embeddings
+
+
+def find_text_dirs(pipe_dir, kind):
+    """(``<pipe>/text_encoder``, ``<pipe>/tokenizer``) for a ``gemma2`` or ``t5`` pipe, None when either is absent."""
+    if kind == "t5":
+        from .t5 import find_t5_dirs
+        return find_t5_dirs(pipe_dir)
+    from .gemma2 import find_text_encoder_dirs
+    return find_text_encoder_dirs(pipe_dir)
+
+
+def text_encoder_model_type(pipe_dir):
+    """``model_type`` of ``<pipe>/text_encoder/config.json``; None without that file."""
+    path = os.path.join(pipe_dir or "", "text_encoder", "config.json")
+    if not os.path.isfile(path):
+        return None
+    with open(path) as f:
+        return json.load(f).get("model_type")
+
+
 def load_encoder(pipe_dir: str, device="cuda", softcap=True):
-    """(Gemma2EncoderHIP, tokenizer) of a SANA pipeline directory."""
+    """(encoder, tokenizer) of a pipeline directory: ``T5EncoderHIP`` with T5's tokenizer when ``text_encoder/config.json``
+    says ``model_type`` ``t5`` (PixArt-Sigma; ``softcap`` does not apply), else ``Gemma2EncoderHIP`` (SANA)."""
+    kind = text_encoder_model_type(pipe_dir)
+    if kind == "t5":
+        from .t5 import T5EncoderHIP, find_t5_dirs
+        dirs = find_t5_dirs(pipe_dir)
+        if dirs is None:
+            raise FileNotFoundError(f"{pipe_dir!r} holds no text_encoder/config.json + tokenizer/tokenizer.json or spiece.model")
+        return T5EncoderHIP.from_pretrained(dirs[0], device=device), load_t5_tokenizer(dirs[1])
+    if kind not in (None, "gemma2"):
+        raise NotImplementedError(f"{pipe_dir!r}: text encoder model_type {kind!r} is not built (gemma2 and t5 are)")
     from .gemma2 import Gemma2EncoderHIP, find_text_encoder_dirs
     dirs = find_text_encoder_dirs(pipe_dir)
     if dirs is None:
@@ -125,8 +255,9 @@ def load_encoder(pipe_dir: str, device="cuda", softcap=True):
 
 def main(argv=None, loader=load_encoder) -> None:
     ap = argparse.ArgumentParser(prog="python -m yat_amd.encode_prompts",
-                                 description="encode captions / prompts into SANA prompt embeddings on the HIP Gemma-2 encoder")
-    ap.add_argument("--pipe", required=True, help="SANA pipeline directory (text_encoder/ and tokenizer/)")
+                                 description="encode captions / prompts into prompt embeddings on the HIP text encoder of a SANA "
+                                             "(Gemma-2) or PixArt-Sigma (T5) pipeline directory")
+    ap.add_argument("--pipe", required=True, help="pipeline directory (text_encoder/ and tokenizer/)")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--no-softcap", action="store_true", help="drop the attention soft cap (what transformers' SDPA path computes)")
     ap.add_argument("--empty", metavar="OUT.pt", help="write the empty prompt's embedding (empty_embeds.pt)")
@@ -137,6 +268,7 @@ def main(argv=None, loader=load_encoder) -> None:
     encoder, tokenizer = loader(a.pipe, device=a.device, softcap=not a.no_softcap)
     if hasattr(encoder, "describe"):
         print(encoder.describe())
+    extract_embeddings, validation_embeddings = rules_for(encoder)
     if a.captions:
         texts = []
         for path in a.captions:

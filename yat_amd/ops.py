@@ -978,3 +978,31 @@ def gemma_attn_fwd(qkv2d, row_offsets_i32, B, Hq, Hkv, dh, max_len, scale, softc
                                    out.stride(0), _stream())
     _l.check(rc, "yat_gemma_attn_fwd")
     return out
+
+
+# ------------------------------------------------------------------------------------ T5 text encoder (yat_amd/t5.py)
+def t5_rmsnorm(x2d, w, y, eps=1e-6, residual=None, sum_out=None):
+    """T5LayerNorm, two roundings; with ``residual``: ``sum_out`` = bf16(residual + x) is stored (default: in place on
+    ``residual``) and ``y`` is its norm (yat_t5_rmsnorm)."""
+    if residual is not None and sum_out is None:
+        sum_out = residual
+    _chk_bf16(x2d, w, y, residual, sum_out)
+    M, D = x2d.shape
+    rc = _lib().yat_t5_rmsnorm(M, D, float(eps), _p(x2d), _p(w), _p(residual), _p(sum_out if residual is not None else None),
+                               _p(y), _stream())
+    _l.check(rc, "yat_t5_rmsnorm")
+    return y
+
+
+def t5_attn_fwd(qkv2d, row_offsets_i32, B, H, dh, max_len, bias_rel, out):
+    """Bidirectional unscaled attention with T5's relative-position bias over packed prompts (yat_t5_attn_fwd); qkv2d =
+    [q | k | v] blocks, ``row_offsets_i32``: int32 [B + 1] on the device, ``bias_rel``: bf16 [H, 2 * max_len - 1]."""
+    _chk_bf16(qkv2d, bias_rel, out)
+    if row_offsets_i32.dtype != torch.int32 or row_offsets_i32.numel() != B + 1:
+        raise ValueError("t5_attn_fwd: row_offsets must be int32 [B + 1]")
+    if bias_rel.dim() != 2 or not bias_rel.is_contiguous() or bias_rel.shape[0] != H or bias_rel.shape[1] != 2 * int(max_len) - 1:
+        raise ValueError("t5_attn_fwd: bias_rel must be a contiguous [H, 2 * max_len - 1] table")
+    rc = _lib().yat_t5_attn_fwd(B, qkv2d.shape[0], H, dh, int(max_len), _p(qkv2d), qkv2d.stride(0), 0, H * dh, 2 * H * dh,
+                                _p(bias_rel), _p(row_offsets_i32), _p(out), out.stride(0), _stream())
+    _l.check(rc, "yat_t5_attn_fwd")
+    return out
