@@ -140,13 +140,13 @@ def test_tokenizer_rule_matches_transformers(spiece):
     for text in texts:
         clean = text.lower().strip()
         want = want_tok(clean, padding="max_length", max_length=300, truncation=True, add_special_tokens=True)
-        ids = EP.tokenize_prompts_t5(tok, [text])[0]
+        ids = EP.tokenize_t5_prompts(tok, [text])[0][0]
         n = sum(want["attention_mask"])
         assert ids == list(want["input_ids"][:n]), text[:40]
         assert all(i == 0 for i in want["input_ids"][n:]) and len(want["input_ids"]) == 300
         assert ids[-1] == 1 and len(ids) <= 300
-    assert EP.tokenize_prompts_t5(tok, "")[0] == [1]
-    assert [len(EP.tokenize_prompts_t5(tok, [t])[0]) for t in texts[2:5]] == [300, 300, 300]
+    assert EP.tokenize_t5_prompts(tok, "")[0][0] == [1]
+    assert [len(EP.tokenize_t5_prompts(tok, [t])[0][0]) for t in texts[2:5]] == [300, 300, 300]
 
 
 def test_tokenizer_json_is_preferred_and_gets_eos(tmp_path):
@@ -160,8 +160,8 @@ def test_tokenizer_json_is_preferred_and_gets_eos(tmp_path):
     tok.post_processor = TemplateProcessing(single="$A </s>", special_tokens=[("</s>", 1)])
     tok.save(str(tmp_path / "tokenizer.json"))
     t = EP.load_t5_tokenizer(str(tmp_path))
-    assert EP.tokenize_prompts_t5(t, [" A Cat", ""]) == [[3, 4, 1], [1]]
-    assert EP.tokenize_prompts_t5(t, ["a " * 400])[0] == [3] * 299 + [1]
+    assert EP.tokenize_t5_prompts(t, [" A Cat", ""])[0] == [[3, 4, 1], [1]]
+    assert EP.tokenize_t5_prompts(t, ["a " * 400])[0][0] == [3] * 299 + [1]
 
 
 # ------------------------------------------------------------------------------------------------------------------ loader
@@ -249,15 +249,15 @@ class StubEncoder:
 def test_prompt_rules(spiece):
     tok = EP.load_t5_tokenizer(spiece)
     enc = StubEncoder()
-    embs = EP.extract_embeddings_t5(enc, tok, ["  A Cat ", ""], max_batch=3)
+    embs = EP.extract_embeddings(enc, tok, ["  A Cat ", ""], max_batch=3)
     n = len(tok._pieces("a cat"))
     assert [tuple(e.shape) for e in embs] == [(n + 1, 16), (1, 16)]
     assert enc.calls[0] == ([tok._pieces("a cat") + [1], [1]], 3)
-    emb, mask = EP.encode_prompt_t5(enc, tok, ["a cat", ""])
+    emb, mask = EP.encode_prompt(enc, tok, ["a cat", ""])
     assert emb.shape == (2, 300, 16) and mask.shape == (2, 300) and mask.dtype == torch.int64 and emb.dtype == BF
     assert mask.sum(1).tolist() == [n + 1, 1] and not emb[0, n + 1:].any() and not emb[1, 1:].any()
     assert torch.equal(emb[0, :n + 1], embs[0])
-    out = EP.validation_embeddings_t5(enc, tok, ["a cat", "w1 w2"])
+    out = EP.validation_embeddings(enc, tok, ["a cat", "w1 w2"])
     assert len(out) == 2
     for pe, pm, ne, nm in out:
         assert pe.shape == ne.shape == (1, 300, 16) and pm.shape == nm.shape == (1, 300) and pe.dtype == BF

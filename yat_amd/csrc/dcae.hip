@@ -10,6 +10,7 @@
 //   rmsnorm_bias    diffusers RMSNorm(eps, elementwise_affine, bias) with its bf16 rounding, + residual, + ReLU.
 //   image_to_uint8  VaeImageProcessor.postprocess: (x / 2 + 0.5).clamp(0, 1) in bf16, then numpy's round(x * 255).
 #include "dcae_conv.hpp"
+#include "rownorm_lpr.hpp"
 
 namespace {
 
@@ -167,46 +168,27 @@ __global__ __launch_bounds__(256) void msla_aggregate_kernel(int H, int W, int C
 }
 
 // -------------------------------------------------------------------------------------------------------- rmsnorm_bias
-// LPR lanes per row (a power of two dividing D / 8, at most 64); two passes over the row (the second re-reads it from L1).
-__global__ __launch_bounds__(256) void rmsnorm_bias_kernel(int M, int D, int lpr, float eps, const bf16_t* __restrict__ x,
-                                                           const bf16_t* __restrict__ w, const bf16_t* __restrict__ bias,
-                                                           const bf16_t* res, int relu, bf16_t* y) {
-    const int rows_per_block = 256 / lpr;
-    const int r = blockIdx.x * rows_per_block + threadIdx.x / lpr;
-    const int l = threadIdx.x & (lpr - 1);
-    const int nch = D >> 3;
-    const bool live = r < M;
-    const bf16_t* xr = x + (int64_t)(live ? r : 0) * D;
-    float ss = 0.f;
-    if (live) {
-        for (int c = l; c < nch; c += lpr) {
-            float v[8];
-            unpack8(*reinterpret_cast<const u32x4*>(xr + c * 8), v);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) ss = __builtin_fmaf(v[e], v[e], ss);
-        }
-    }
-    for (int o = 1; o < lpr; o <<= 1) ss += __shfl_xor(ss, o, 64);
-    if (!live) return;
-    const float rs = 1.0f / sqrtf(ss / (float)D + eps);
-    for (int c = l; c < nch; c += lpr) {
-        float v[8], wv[8], bv[8];
-        unpack8(*reinterpret_cast<const u32x4*>(xr + c * 8), v);
-        unpack8(*reinterpret_cast<const u32x4*>(w + c * 8), wv);
-        if (bias) unpack8(*reinterpret_cast<const u32x4*>(bias + c * 8), bv);
-        float rv[8];
-        if (res) unpack8(*reinterpret_cast<const u32x4*>(res + (int64_t)r * D + c * 8), rv);
+// The row walk is csrc/rownorm_lpr.hpp's; diffusers' RMSNorm rounds the normalised value, the weight product, the bias add and
+// the residual add each on its own.
+struct RmsnormBiasPost {
+    typedef RowOutInPlace out_t;                           // y may be res
+    const bf16_t* bias;
+    const bf16_t* res;
+    int relu;
+    __device__ __forceinline__ void operator()(float* v, const float* w, int64_t off, int col) const {
+        float bv[8], rv[8];
+        if (bias) unpack8(*reinterpret_cast<const u32x4*>(bias + col), bv);
+        if (res) unpack8(*reinterpret_cast<const u32x4*>(res + off), rv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            float t = rbf(rbf(v[e] * rs) * wv[e]);
+            float t = rbf(rbf(v[e]) * w[e]);
             if (bias) t = rbf(t + bv[e]);
             if (res) t = rbf(t + rv[e]);
             if (relu) t = fmaxf(t, 0.f);
             v[e] = t;
         }
-        *reinterpret_cast<u32x4*>(y + (int64_t)r * D + c * 8) = pack8(v);
     }
-}
+};
 
 // ------------------------------------------------------------------------------------------------------ image_to_uint8
 __global__ __launch_bounds__(256) void image_to_uint8_kernel(int64_t n, const bf16_t* __restrict__ x, uint8_t* __restrict__ y) {
@@ -270,14 +252,8 @@ int yat_dcae_msla_aggregate(int B, int H, int W, int C3, const void* qkv, const 
 int yat_dcae_rmsnorm_bias(int M, int D, float eps, const void* x, const void* w, const void* b, const void* residual,
                           int relu, void* y, yat_stream_t stream) {
     if (M <= 0 || D <= 0 || (D & 7) || !(eps >= 0.f) || !x || !w || !y || (relu != 0 && relu != 1)) return YAT_EINVAL;
-    int lpr = 1;
-    while (lpr < 64 && ((D >> 3) % (lpr * 2)) == 0) lpr *= 2;
-    const int rows_per_block = 256 / lpr;
-    hipLaunchKernelGGL(rmsnorm_bias_kernel, dim3((unsigned)((M + rows_per_block - 1) / rows_per_block)), dim3(256), 0,
-                       (hipStream_t)stream, M, D, lpr, eps, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)b,
-                       (const bf16_t*)residual, relu, (bf16_t*)y);
-    YAT_CHECK_LAUNCH();
-    return YAT_OK;
+    return launch_rownorm_lpr(M, D, eps, x, w, y, RowIdentity{}, RmsnormBiasPost{(const bf16_t*)b, (const bf16_t*)residual, relu},
+                              (hipStream_t)stream);
 }
 
 int yat_dcae_image_to_uint8(int64_t n, const void* x, void* out, yat_stream_t stream) {

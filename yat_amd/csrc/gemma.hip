@@ -10,7 +10,8 @@
 //   rope_qk     x' = bf16(bf16(x cos) + bf16(rotate_half(x) sin))      apply_rotary_pos_emb on the q and k column blocks, in place
 //   geglu       out = bf16(bf16(gelu_tanh(gate)) * up)                 Gemma2MLP's act_fn(gate_proj(x)) * up_proj(x)
 //   attention   causal, grouped-query, soft-capped softmax attention at head dim 256 (below)
-#include "common.hpp"
+#include "attn_prefill.hpp"
+#include "rownorm_lpr.hpp"
 
 namespace {
 
@@ -34,41 +35,21 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(int64_t nchunk, int nch
 }
 
 // ------------------------------------------------------------------------------------------------------------- rmsnorm
-// LPR lanes per row (a power of two dividing D / 8, at most 64); two passes over the row (the second re-reads it from L1).
-__global__ __launch_bounds__(256) void gemma_rmsnorm_kernel(int M, int D, int lpr, float eps, const bf16_t* __restrict__ x,
-                                                            const bf16_t* __restrict__ w, const bf16_t* res, bf16_t* y) {
-    const int rows_per_block = 256 / lpr;
-    const int r = blockIdx.x * rows_per_block + threadIdx.x / lpr;
-    const int l = threadIdx.x & (lpr - 1);
-    const int nch = D >> 3;
-    const bool live = r < M;
-    const bf16_t* xr = x + (int64_t)(live ? r : 0) * D;
-    float ss = 0.f;
-    if (live) {
-        for (int c = l; c < nch; c += lpr) {
-            float v[8];
-            unpack8(*reinterpret_cast<const u32x4*>(xr + c * 8), v);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) ss = __builtin_fmaf(v[e], v[e], ss);
-        }
-    }
-    for (int o = 1; o < lpr; o <<= 1) ss += __shfl_xor(ss, o, 64);
-    if (!live) return;
-    const float rs = 1.0f / sqrtf(ss / (float)D + eps);
-    for (int c = l; c < nch; c += lpr) {
-        float v[8], wv[8], rv[8];
-        unpack8(*reinterpret_cast<const u32x4*>(xr + c * 8), v);
-        unpack8(*reinterpret_cast<const u32x4*>(w + c * 8), wv);
-        if (res) unpack8(*reinterpret_cast<const u32x4*>(res + (int64_t)r * D + c * 8), rv);
+// The row walk is csrc/rownorm_lpr.hpp's; Gemma2RMSNorm finishes an element with ONE rounding and 1 + w, then the residual add.
+struct GemmaNormPost {
+    typedef RowOutInPlace out_t;                           // y may be res
+    const bf16_t* res;
+    __device__ __forceinline__ void operator()(float* v, const float* w, int64_t off, int) const {
+        float rv[8];
+        if (res) unpack8(*reinterpret_cast<const u32x4*>(res + off), rv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            float t = (v[e] * rs) * (1.0f + wv[e]);
+            float t = v[e] * (1.0f + w[e]);
             if (res) t = rv[e] + rbf(t);
             v[e] = t;
         }
-        *reinterpret_cast<u32x4*>(y + (int64_t)r * D + c * 8) = pack8(v);
     }
-}
+};
 
 // ------------------------------------------------------------------------------------------------------------- rope_qk
 // thread = (row, head, 8-column chunk c of the lower half): rotates columns [8c, 8c + 8) and [dh/2 + 8c, dh/2 + 8c + 8).
@@ -134,9 +115,6 @@ constexpr int GA_DH = 256, GA_KT = 64, GA_SUB = 32 * 256;       // one [32][128]
 constexpr int GA_MAT = 4 * GA_SUB, GA_STAGE = 2 * GA_MAT;       // K (or V) of one stage; K then V
 constexpr int GA_LDS = 2 * GA_STAGE;
 constexpr int GA_MAX_LEN = 1024;
-constexpr float GA_LOG2E = 1.4426950408889634f;
-constexpr float GA_LAZY_LOG2 = 8.0f;                            // rescale threshold in log2 units (P <= 2^8)
-
 struct GemmaAttnP {
     int rows, Hq, G, ld, ldo;
     float scale, cap;
@@ -144,34 +122,6 @@ struct GemmaAttnP {
     const int* off;
     bf16_t* out;
 };
-
-__device__ __forceinline__ bf16x8 ga_frag_row(const char* lds, int row0, int ks, int lane) {
-    const uint32_t r = row0 + (lane & 15);
-    const uint32_t c = (ks * 4 + (lane >> 4)) ^ (r & 15);
-    return lds_read8(lds, r * 256 + c * 16);
-}
-// operand in ACCUMULATOR k order from a TR image: idx = col0 + (lane & 15); k slot (g, j): row 4g + j (j < 4), 16 + 4g + j - 4
-__device__ __forceinline__ bf16x8 ga_frag_tr(const char* lds, int col0, int lane) {
-    const uint32_t g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const uint32_t col = col0 + 4 * p;
-    const uint32_t r0 = 4 * g + q, r1 = r0 + 16;
-    const uint32_t c0 = (col >> 3) ^ ((r0 & 7) << 1), c1 = (col >> 3) ^ ((r1 & 7) << 1);
-    return cat4(lds_read_tr4(lds, r0 * 256 + c0 * 16 + (p & 1) * 8), lds_read_tr4(lds, r1 * 256 + c1 * 16 + (p & 1) * 8));
-}
-__device__ __forceinline__ bf16x8 ga_acc_to_frag(const f32x4& a, const f32x4& b) {
-    bf16x8 r;
-    r[0] = (__bf16)a[0]; r[1] = (__bf16)a[1]; r[2] = (__bf16)a[2]; r[3] = (__bf16)a[3];
-    r[4] = (__bf16)b[0]; r[5] = (__bf16)b[1]; r[6] = (__bf16)b[2]; r[7] = (__bf16)b[3];
-    return r;
-}
-__device__ __forceinline__ float ga_group_max(float v) {      // across the 4 lane groups that share lane & 15
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float ga_group_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
-}
 
 template <int NW, int HPW>
 __global__ __launch_bounds__(NW * 64) void gemma_attn_kernel(GemmaAttnP p) {
@@ -209,27 +159,16 @@ __global__ __launch_bounds__(NW * 64) void gemma_attn_kernel(GemmaAttnP p) {
     stage(0, smem);
 
     bf16x8 qf[KS];
-    {
-        const int qi = sq0 + li;
-        const bf16_t* qp = p.q + (int64_t)(prow0 + qi) * p.ld + head * GA_DH + 8 * g;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            bf16x8 z;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) z[e] = (__bf16)0.0f;
-            if (qi < len) z = *reinterpret_cast<const bf16x8*>(qp + ks * 32);
-            qf[ks] = z;
-        }
-    }
+    load_q_frags<KS>(qf, p.q + (int64_t)(prow0 + sq0 + li) * p.ld + head * GA_DH, sq0 + li < len, g);
     f32x4 o[DT];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m = -1e30f, l = 0.f;                                 // running maximum in log2 units, row sum
     const bool capped = p.cap > 0.f;
     // logit in log2 units: t = s * c_lin (no cap), or c_cap * tanh(s * scale / cap) with tanh(y) = 1 - 2 / (1 + e^(2y))
-    const float c_lin = p.scale * GA_LOG2E;
-    const float c_exp = capped ? 2.0f * GA_LOG2E * p.scale / p.cap : 0.f;
-    const float c_cap = p.cap * GA_LOG2E;
+    const float c_lin = p.scale * LOG2E;
+    const float c_exp = capped ? 2.0f * LOG2E * p.scale / p.cap : 0.f;
+    const float c_cap = p.cap * LOG2E;
 
     const int ntiles = q0 / GA_KT + 1;                         // the last one holds the diagonal
     for (int it = 0; it < ntiles; ++it) {
@@ -250,7 +189,7 @@ __global__ __launch_bounds__(NW * 64) void gemma_attn_kernel(GemmaAttnP p) {
                 s[nj] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks)
-                    s[nj] = mfma16(ga_frag_row(Ks + (ks / 4) * GA_SUB, nj * 16, ks % 4, lane), qf[ks], s[nj]);
+                    s[nj] = mfma16(frag_row256(Ks + (ks / 4) * GA_SUB, nj * 16, ks % 4, lane), qf[ks], s[nj]);
             }
 #pragma unroll
             for (int nj = 0; nj < 2; ++nj)
@@ -266,46 +205,13 @@ __global__ __launch_bounds__(NW * 64) void gemma_attn_kernel(GemmaAttnP p) {
                     for (int r = 0; r < 4; ++r)
                         if (kh0 + nj * 16 + 4 * g + r > sq0 + li) s[nj][r] = -1e30f;
             }
-            float t = -1e30f;
+            const bf16x8 pf = online_softmax_step<DT>(s, m, l, o, 1.0f);
 #pragma unroll
-            for (int nj = 0; nj < 2; ++nj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) t = fmaxf(t, s[nj][r]);
-            const float mx = ga_group_max(t);
-            if (__builtin_amdgcn_ballot_w64(mx > m + GA_LAZY_LOG2) != 0) {     // uniform; after the first tiles: rare
-                const float mn = fmaxf(m, mx);
-                const float alpha = __builtin_amdgcn_exp2f(m - mn);
-                m = mn;
-                l *= alpha;
-#pragma unroll
-                for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
-            }
-            float rs = 0.f;
-#pragma unroll
-            for (int nj = 0; nj < 2; ++nj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float e = rbf(__builtin_amdgcn_exp2f(s[nj][r] - m));
-                    s[nj][r] = e;
-                    rs += e;
-                }
-            l += ga_group_sum(rs);
-            const bf16x8 pf = ga_acc_to_frag(s[0], s[1]);
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) o[dt] = mfma16(ga_frag_tr(Vs + (dt / 8) * GA_SUB, (dt % 8) * 16, lane), pf, o[dt]);
+            for (int dt = 0; dt < DT; ++dt) o[dt] = mfma16(frag_tr256(Vs + (dt / 8) * GA_SUB, (dt % 8) * 16, lane), pf, o[dt]);
         }
     }
     const int qi = sq0 + li;
-    if (qi < len) {
-        const float inv = 1.0f / l;
-        bf16_t* op = p.out + (int64_t)(prow0 + qi) * p.ldo + head * GA_DH;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-            *reinterpret_cast<u32x2*>(op + dt * 16 + 4 * g) =
-                pack4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv);
-    }
+    if (qi < len) store_o<DT>(p.out + (int64_t)(prow0 + qi) * p.ldo + head * GA_DH, o, l, g);
 }
 
 template <int NW, int HPW>
@@ -342,14 +248,7 @@ int yat_embed_rows(int rows, int D, int vocab, const void* ids, const void* tabl
 int yat_gemma_rmsnorm(int M, int D, float eps, const void* x, const void* w, const void* residual, void* y, yat_stream_t stream) {
     if (M <= 0 || D <= 0 || (D & 7) || !(eps >= 0.f) || !x || !w || !y) return YAT_EINVAL;
     if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)residual) & 15) return YAT_EINVAL;
-    int lpr = 1;
-    while (lpr < 64 && ((D >> 3) % (lpr * 2)) == 0) lpr *= 2;
-    const int rows_per_block = 256 / lpr;
-    hipLaunchKernelGGL(gemma_rmsnorm_kernel, dim3((unsigned)((M + rows_per_block - 1) / rows_per_block)), dim3(256), 0,
-                       (hipStream_t)stream, M, D, lpr, eps, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)residual,
-                       (bf16_t*)y);
-    YAT_CHECK_LAUNCH();
-    return YAT_OK;
+    return launch_rownorm_lpr(M, D, eps, x, w, y, RowIdentity{}, GemmaNormPost{(const bf16_t*)residual}, (hipStream_t)stream);
 }
 
 int yat_rope_qk(int rows, int heads, int dh, int max_len, void* qkv, int ld, const void* positions, const void* cos_table,

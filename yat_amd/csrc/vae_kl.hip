@@ -12,7 +12,7 @@
 //   attention   F.scaled_dot_product_attention(q, k, v) with one head of dh in {64, 512}, no mask (the mid-block Attention):
 //               flash-style, scores and the online softmax in fp32, P rounded to bf16 for the P V product, fp32 accumulation;
 //               the row sum adds the same rounded P, so the weights that multiply V sum to one exactly.
-#include "common.hpp"
+#include "attn_prefill.hpp"
 
 namespace {
 
@@ -143,8 +143,6 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(int64_t nchunk, int HW, i
 //   dh 512: stage = (K + V) 32 x 512 bf16 = 64 KiB, two stages = 128 KiB -> one workgroup per CU.
 constexpr int AT_KEYS = 32;
 constexpr int AT_SUB = AT_KEYS * 256;               // one [32][128] bf16 image
-constexpr float AT_LOG2E = 1.4426950408889634f;
-constexpr float AT_LAZY_LOG2 = 8.0f;                // rescale threshold in log2 units (P <= 2^8, exact in fp32 / bf16)
 
 struct AttnP {
     int N, ld, ldo;
@@ -152,34 +150,6 @@ struct AttnP {
     const bf16_t* q; const bf16_t* k; const bf16_t* v;
     bf16_t* out;
 };
-
-__device__ __forceinline__ bf16x8 at_frag_row(const char* lds, int row0, int ks, int lane) {
-    const uint32_t r = row0 + (lane & 15);
-    const uint32_t c = (ks * 4 + (lane >> 4)) ^ (r & 15);
-    return lds_read8(lds, r * 256 + c * 16);
-}
-// operand in ACCUMULATOR k order from a TR image: idx = col0 + (lane & 15); k slot (g, j): row 4g + j (j < 4), 16 + 4g + j - 4
-__device__ __forceinline__ bf16x8 at_frag_tr(const char* lds, int col0, int lane) {
-    const uint32_t g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const uint32_t col = col0 + 4 * p;
-    const uint32_t r0 = 4 * g + q, r1 = r0 + 16;
-    const uint32_t c0 = (col >> 3) ^ ((r0 & 7) << 1), c1 = (col >> 3) ^ ((r1 & 7) << 1);
-    return cat4(lds_read_tr4(lds, r0 * 256 + c0 * 16 + (p & 1) * 8), lds_read_tr4(lds, r1 * 256 + c1 * 16 + (p & 1) * 8));
-}
-__device__ __forceinline__ bf16x8 at_acc_to_frag(const f32x4& a, const f32x4& b) {
-    bf16x8 r;
-    r[0] = (__bf16)a[0]; r[1] = (__bf16)a[1]; r[2] = (__bf16)a[2]; r[3] = (__bf16)a[3];
-    r[4] = (__bf16)b[0]; r[5] = (__bf16)b[1]; r[6] = (__bf16)b[2]; r[7] = (__bf16)b[3];
-    return r;
-}
-__device__ __forceinline__ float at_group_max(float v) {      // across the 4 lane groups that share lane & 15
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float at_group_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
-}
 
 template <int DH>
 __global__ __launch_bounds__(256) void vae_attn_kernel(AttnP p) {
@@ -219,21 +189,13 @@ __global__ __launch_bounds__(256) void vae_attn_kernel(AttnP p) {
     bf16x8 qf[KS];
     {
         const int64_t qr = row0 + q0 + li;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            bf16x8 z;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) z[e] = (__bf16)0.0f;
-            if (qr < rowl) z = *reinterpret_cast<const bf16x8*>(p.q + qr * p.ld + ks * 32 + 8 * g);
-            qf[ks] = z;
-        }
+        load_q_frags<KS>(qf, p.q + qr * p.ld, qr < rowl, g);
     }
     f32x4 o[DT];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m = -1e30f, l = 0.f;
-    const float ce = p.scale * AT_LOG2E;                // exp2 argument = s * ce - m * ce on the raw scores
-    const float lazy = AT_LAZY_LOG2 / ce;
+    const float ce = p.scale * LOG2E;                   // exp2 argument = s * ce - m * ce on the raw scores
 
     int it = 0;
     for (int k0 = 0; k0 < p.N; k0 += AT_KEYS, ++it) {
@@ -250,7 +212,7 @@ __global__ __launch_bounds__(256) void vae_attn_kernel(AttnP p) {
             s[nj] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
-                s[nj] = mfma16(at_frag_row(Ks + (ks / 4) * AT_SUB, nj * 16, ks % 4, lane), qf[ks], s[nj]);
+                s[nj] = mfma16(frag_row256(Ks + (ks / 4) * AT_SUB, nj * 16, ks % 4, lane), qf[ks], s[nj]);
         }
         if (k0 + AT_KEYS > p.N) {                          // uniform: keys past N in the last tile vanish from the softmax
 #pragma unroll
@@ -259,46 +221,12 @@ __global__ __launch_bounds__(256) void vae_attn_kernel(AttnP p) {
                 for (int r = 0; r < 4; ++r)
                     if (k0 + nj * 16 + 4 * g + r >= p.N) s[nj][r] = -1e30f;
         }
-        float t = -1e30f;
+        const bf16x8 pf = online_softmax_step<DT>(s, m, l, o, ce);
 #pragma unroll
-        for (int nj = 0; nj < 2; ++nj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) t = fmaxf(t, s[nj][r]);
-        const float mx = at_group_max(t);
-        if (__builtin_amdgcn_ballot_w64(mx > m + lazy) != 0) {   // uniform; after the first tiles: rare
-            const float mn = fmaxf(m, mx);
-            const float alpha = __builtin_amdgcn_exp2f((m - mn) * ce);
-            m = mn;
-            l *= alpha;
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
-        }
-        const float nm2 = -m * ce;
-        float rs = 0.f;
-#pragma unroll
-        for (int nj = 0; nj < 2; ++nj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = rbf(__builtin_amdgcn_exp2f(__builtin_fmaf(s[nj][r], ce, nm2)));
-                s[nj][r] = e;
-                rs += e;
-            }
-        l += at_group_sum(rs);
-        const bf16x8 pf = at_acc_to_frag(s[0], s[1]);
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) o[dt] = mfma16(at_frag_tr(Vs + (dt / 8) * AT_SUB, (dt % 8) * 16, lane), pf, o[dt]);
+        for (int dt = 0; dt < DT; ++dt) o[dt] = mfma16(frag_tr256(Vs + (dt / 8) * AT_SUB, (dt % 8) * 16, lane), pf, o[dt]);
     }
     const int qi = q0 + li;
-    if (qi < p.N) {
-        const float inv = 1.0f / l;
-        bf16_t* op = p.out + (row0 + qi) * p.ldo;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-            *reinterpret_cast<u32x2*>(op + dt * 16 + 4 * g) =
-                pack4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv);
-    }
+    if (qi < p.N) store_o<DT>(p.out + (row0 + qi) * p.ldo, o, l, g);
 }
 
 template <int DH>

@@ -93,10 +93,9 @@ class DiTTrainer(Model):
         return enc
 
     def extract_embeddings(self, captions):
-        from .encode_prompts import rules_for
+        from .encode_prompts import extract_embeddings
         encoder, tokenizer = self._text_encoder()
-        return rules_for(encoder)[0](encoder, tokenizer, captions,
-                                     max_batch=getattr(self.params, "text_encoder_max_batch_size", None))
+        return extract_embeddings(encoder, tokenizer, captions, max_batch=getattr(self.params, "text_encoder_max_batch_size", None))
 
     def load_empty_embeddings(self):
         emb = super().load_empty_embeddings()
@@ -115,8 +114,8 @@ class DiTTrainer(Model):
             encoder, tokenizer = self._text_encoder()
         except NotImplementedError:
             return None
-        from .encode_prompts import rules_for
-        self.validation_embeds = rules_for(encoder)[1](encoder, tokenizer, list(self.params.validation_prompts or []))
+        from .encode_prompts import validation_embeddings
+        self.validation_embeds = validation_embeddings(encoder, tokenizer, list(self.params.validation_prompts or []))
         encoder.free()
         self.text_encoder = None
         return self.validation_embeds

@@ -20,8 +20,13 @@ from __future__ import annotations
 import argparse
 import json
 import os
+from collections import namedtuple
 
 import torch
+
+from . import text_common
+from .gemma2 import Gemma2EncoderHIP
+from .t5 import T5EncoderHIP
 
 MAX_SEQUENCE_LENGTH = 300             # SanaPipeline.encode_prompt's max_sequence_length default
 
@@ -90,34 +95,7 @@ def select_rows(emb: torch.Tensor, max_length_all: int, max_sequence_length=MAX_
     return out, real.to(torch.int64)
 
 
-def encode_prompt(encoder, tokenizer, prompts, complex_human_instruction=None, max_batch=None):
-    """``pipe.encode_prompt(prompts, complex_human_instruction=..., do_classifier_free_guidance=False)`` -> (embeds ``[B, 300,
-    C]`` bf16, mask ``[B, 300]`` int64), both on the encoder's device.  ``encoder.encode`` maps id tensors to ``[L, C]`` rows."""
-    ids, max_length_all = tokenize_prompts(tokenizer, prompts, complex_human_instruction)
-    rows = encoder.encode([torch.tensor(i, dtype=torch.int64) for i in ids], max_batch=max_batch)
-    picked = [select_rows(r, max_length_all) for r in rows]
-    return torch.stack([p[0] for p in picked]), torch.stack([p[1] for p in picked]).to(picked[0][0].device)
-
-
-def extract_embeddings(encoder, tokenizer, captions, max_batch=None):
-    """train_sana.py:84-94: ``encode_prompt`` without an instruction, then the mask-true rows of each prompt -- without an
-    instruction those are the rows of its (truncated) tokens, so nothing is padded and selected first."""
-    ids, _ = tokenize_prompts(tokenizer, list(captions))
-    return encoder.encode([torch.tensor(i, dtype=torch.int64) for i in ids], max_batch=max_batch)
-
-
-def validation_embeddings(encoder, tokenizer, prompts):
-    """train_sana.py:124-129: per prompt ``pipe.encode_prompt(prompt, complex_human_instruction=...)`` with classifier-free
-    guidance on and the default negative prompt ``""`` -> a list of (prompt_embeds, mask, negative_embeds, negative_mask)."""
-    out = []
-    neg, neg_mask = encode_prompt(encoder, tokenizer, [""])
-    for p in prompts:
-        pe, pm = encode_prompt(encoder, tokenizer, [p], COMPLEX_HUMAN_INSTRUCTION)
-        out.append((pe.cpu(), pm.cpu(), neg.cpu().clone(), neg_mask.cpu().clone()))
-    return out
-
-
-# ------------------------------------------------------------------------------------------------ T5 (PixArt-Sigma) rules
+# ---------------------------------------------------------------------------------------- T5 (PixArt-Sigma) tokenizer rules
 class T5Tokenizer:
     """T5's tokenizer rule over a sentencepiece model: ``tokenize(text, max_length)`` = the pieces cut to ``max_length - 1``,
     then EOS (the id of ``</s>``) -- what ``transformers.T5Tokenizer(text, max_length=..., truncation=True,
@@ -159,69 +137,86 @@ def load_t5_tokenizer(tokenizer_dir: str) -> T5Tokenizer:
     return T5Tokenizer(lambda text: sp.encode(text), eos)
 
 
-def tokenize_prompts_t5(tokenizer: T5Tokenizer, prompts, max_sequence_length=MAX_SEQUENCE_LENGTH):
+def tokenize_t5_prompts(tokenizer: T5Tokenizer, prompts, complex_human_instruction=None, max_sequence_length=MAX_SEQUENCE_LENGTH):
     """The prompt rules of diffusers ``PixArtSigmaPipeline.encode_prompt`` [RECALL: restated from knowledge of upstream
     diffusers, which is not importable here]:
 
     * ``_text_preprocessing`` without ``clean_caption``: ``text.lower().strip()``;
     * ``max_sequence_length = 300``;
     * ``tokenizer(text, padding="max_length", max_length=300, truncation=True, add_special_tokens=True)``: the pieces are cut
-      to 299 and ``</s>`` closes them, then the ids are padded on the right with 0;
+      to 299 and ``</s>`` closes them, then the ids are padded on the right with 0 (``pad_right``);
     * the encoder runs under the attention mask; with classifier-free guidance the negative prompt ``""`` is padded to the
       same 300.
 
-    -> list of id lists without the padding (the empty prompt is ``[eos]``)."""
+    PixArt has no complex human instruction.  -> (list of id lists without the padding (the empty prompt is ``[eos]``),
+    max_sequence_length)."""
+    if complex_human_instruction:
+        raise ValueError("PixArt-Sigma's prompt rules take no complex human instruction")
     if isinstance(prompts, str):
         prompts = [prompts]
-    return [tokenizer.tokenize(p.lower().strip(), max_sequence_length) for p in prompts]
+    return [tokenizer.tokenize(p.lower().strip(), max_sequence_length) for p in prompts], max_sequence_length
 
 
-def extract_embeddings_t5(encoder, tokenizer, captions, max_batch=None):
-    """train_pixart_sigma.py:68-74: ``encode_prompt`` then the mask-true rows of each prompt -- the rows of its real tokens,
-    so nothing is padded first."""
-    ids = tokenize_prompts_t5(tokenizer, list(captions))
+def pad_right(emb: torch.Tensor, max_length_all: int):
+    """``emb``: the ``[L, C]`` rows of one prompt's real tokens -> (``[max_length_all, C]``, mask ``[max_length_all]`` int64),
+    padded on the right.  A pad row comes back as zeros with mask 0 (the reference computes something there that the mask
+    then hides)."""
+    L = emb.shape[0]
+    out = torch.zeros(max_length_all, emb.shape[1], dtype=emb.dtype, device=emb.device)
+    out[:L] = emb
+    return out, (torch.arange(max_length_all) < L).to(torch.int64)
+
+
+# ------------------------------------------------------------------------------------------- one rule record per model_type
+# encoder: the class; options: the ``load_encoder`` options it takes; tokenizer_files: what ``<pipe>/tokenizer`` may hold;
+# load_tokenizer(dir); tokenize(tokenizer, prompts, instruction) -> (ids, max_length_all); pad(rows of one prompt,
+# max_length_all) -> ([300, C], mask [300]); instruction: what validate() puts in front of a validation prompt, or None.
+TextRules = namedtuple("TextRules", "encoder options tokenizer_files load_tokenizer tokenize pad instruction")
+RULES = {
+    "gemma2": TextRules(Gemma2EncoderHIP, ("softcap",), ("tokenizer.json",), load_tokenizer, tokenize_prompts, select_rows,
+                        COMPLEX_HUMAN_INSTRUCTION),
+    "t5": TextRules(T5EncoderHIP, (), ("tokenizer.json", "spiece.model"), load_t5_tokenizer, tokenize_t5_prompts, pad_right, None),
+}
+
+
+def rules_for(encoder) -> TextRules:
+    """The prompt rules of an encoder, by its ``model_type`` (absent: Gemma-2's)."""
+    return RULES[getattr(encoder, "model_type", "gemma2")]
+
+
+def extract_embeddings(encoder, tokenizer, captions, max_batch=None):
+    """train_sana.py:84-94, train_pixart_sigma.py:68-74: ``encode_prompt`` without an instruction, then the mask-true rows of
+    each prompt -- without an instruction those are the rows of its (truncated) tokens, so nothing is padded and selected
+    first."""
+    ids, _ = rules_for(encoder).tokenize(tokenizer, list(captions), None)
     return encoder.encode([torch.tensor(i, dtype=torch.int64) for i in ids], max_batch=max_batch)
 
 
-def encode_prompt_t5(encoder, tokenizer, prompts, max_batch=None, max_sequence_length=MAX_SEQUENCE_LENGTH):
-    """``pipe.encode_prompt(prompts, do_classifier_free_guidance=False)`` -> (embeds ``[B, 300, C]`` bf16, mask ``[B, 300]``
-    int64), both on the encoder's device.  A pad row comes back as zeros with mask 0 (the reference computes something there
-    that the mask then hides)."""
-    rows = extract_embeddings_t5(encoder, tokenizer, [prompts] if isinstance(prompts, str) else prompts, max_batch)
-    emb = torch.zeros(len(rows), max_sequence_length, rows[0].shape[1], dtype=rows[0].dtype, device=rows[0].device)
-    mask = torch.zeros(len(rows), max_sequence_length, dtype=torch.int64, device=rows[0].device)
-    for b, r in enumerate(rows):
-        emb[b, :r.shape[0]], mask[b, :r.shape[0]] = r, 1
-    return emb, mask
+def encode_prompt(encoder, tokenizer, prompts, complex_human_instruction=None, max_batch=None):
+    """``pipe.encode_prompt(prompts, complex_human_instruction=..., do_classifier_free_guidance=False)`` -> (embeds ``[B, 300,
+    C]`` bf16, mask ``[B, 300]`` int64), both on the encoder's device.  ``encoder.encode`` maps id tensors to ``[L, C]`` rows."""
+    rules = rules_for(encoder)
+    ids, max_length_all = rules.tokenize(tokenizer, prompts, complex_human_instruction)
+    rows = encoder.encode([torch.tensor(i, dtype=torch.int64) for i in ids], max_batch=max_batch)
+    picked = [rules.pad(r, max_length_all) for r in rows]
+    return torch.stack([p[0] for p in picked]), torch.stack([p[1] for p in picked]).to(picked[0][0].device)
 
 
-def validation_embeddings_t5(encoder, tokenizer, prompts):
-    """train_pixart_sigma.py:97-108: per prompt ``pipe.encode_prompt(prompt)`` with classifier-free guidance on and the
-    default negative prompt ``""`` -> a list of (prompt_embeds, mask, negative_embeds, negative_mask) on the CPU.  PixArt has no
-    complex human instruction."""
+def validation_embeddings(encoder, tokenizer, prompts):
+    """train_sana.py:124-129, train_pixart_sigma.py:97-108: per prompt ``pipe.encode_prompt(prompt)`` (SANA: with the complex
+    human instruction) with classifier-free guidance on and the default negative prompt ``""`` -> a list of (prompt_embeds,
+    mask, negative_embeds, negative_mask) on the CPU."""
     out = []
-    neg, neg_mask = encode_prompt_t5(encoder, tokenizer, [""])
+    neg, neg_mask = encode_prompt(encoder, tokenizer, [""])
     for p in prompts:
-        pe, pm = encode_prompt_t5(encoder, tokenizer, [p])
+        pe, pm = encode_prompt(encoder, tokenizer, [p], rules_for(encoder).instruction)
         out.append((pe.cpu(), pm.cpu(), neg.cpu().clone(), neg_mask.cpu().clone()))
     return out
 
 
-# ------------------------------------------------------------------------------------------------------------- dispatch
-def rules_for(encoder):
-    """(extract_embeddings, validation_embeddings) for an encoder, by its ``model_type`` (absent: Gemma-2's)."""
-    if getattr(encoder, "model_type", "gemma2") == "t5":
-        return extract_embeddings_t5, validation_embeddings_t5
-    return extract_embeddings, validation_embeddings
-
-
 def find_text_dirs(pipe_dir, kind):
     """(``<pipe>/text_encoder``, ``<pipe>/tokenizer``) for a ``gemma2`` or ``t5`` pipe, None when either is absent."""
-    if kind == "t5":
-        from .t5 import find_t5_dirs
-        return find_t5_dirs(pipe_dir)
-    from .gemma2 import find_text_encoder_dirs
-    return find_text_encoder_dirs(pipe_dir)
+    return text_common.find_text_dirs(pipe_dir, RULES.get(kind, RULES["gemma2"]).tokenizer_files)
 
 
 def text_encoder_model_type(pipe_dir):
@@ -236,21 +231,16 @@ def text_encoder_model_type(pipe_dir):
 def load_encoder(pipe_dir: str, device="cuda", softcap=True):
     """(encoder, tokenizer) of a pipeline directory: ``T5EncoderHIP`` with T5's tokenizer when ``text_encoder/config.json``
     says ``model_type`` ``t5`` (PixArt-Sigma; ``softcap`` does not apply), else ``Gemma2EncoderHIP`` (SANA)."""
-    kind = text_encoder_model_type(pipe_dir)
-    if kind == "t5":
-        from .t5 import T5EncoderHIP, find_t5_dirs
-        dirs = find_t5_dirs(pipe_dir)
-        if dirs is None:
-            raise FileNotFoundError(f"{pipe_dir!r} holds no text_encoder/config.json + tokenizer/tokenizer.json or spiece.model")
-        return T5EncoderHIP.from_pretrained(dirs[0], device=device), load_t5_tokenizer(dirs[1])
-    if kind not in (None, "gemma2"):
+    kind = text_encoder_model_type(pipe_dir) or "gemma2"
+    if kind not in RULES:
         raise NotImplementedError(f"{pipe_dir!r}: text encoder model_type {kind!r} is not built (gemma2 and t5 are)")
-    from .gemma2 import Gemma2EncoderHIP, find_text_encoder_dirs
-    dirs = find_text_encoder_dirs(pipe_dir)
+    rules = RULES[kind]
+    dirs = find_text_dirs(pipe_dir, kind)
     if dirs is None:
-        raise FileNotFoundError(f"{pipe_dir!r} holds no text_encoder/config.json + tokenizer/tokenizer.json")
-    tokenizer = load_tokenizer(dirs[1])
-    return Gemma2EncoderHIP.from_pretrained(dirs[0], device=device, softcap=softcap), tokenizer
+        raise FileNotFoundError(f"{pipe_dir!r} holds no text_encoder/config.json + tokenizer/{' or '.join(rules.tokenizer_files)}")
+    tokenizer = rules.load_tokenizer(dirs[1])
+    options = {k: v for k, v in {"softcap": softcap}.items() if k in rules.options}
+    return rules.encoder.from_pretrained(dirs[0], device=device, **options), tokenizer
 
 
 def main(argv=None, loader=load_encoder) -> None:
@@ -268,7 +258,6 @@ def main(argv=None, loader=load_encoder) -> None:
     encoder, tokenizer = loader(a.pipe, device=a.device, softcap=not a.no_softcap)
     if hasattr(encoder, "describe"):
         print(encoder.describe())
-    extract_embeddings, validation_embeddings = rules_for(encoder)
     if a.captions:
         texts = []
         for path in a.captions:

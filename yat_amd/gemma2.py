@@ -22,27 +22,14 @@ Sliding window.  Below ``sliding_window`` tokens Gemma-2's sliding layers equal 
 """
 from __future__ import annotations
 
-import json
-import os
-
 import torch
 
+from .text_common import TextEncoderHIP, read_text_encoder_tensors
 from .vae_common import BF16, check_expected, read_config
 
 MAX_PROMPT = 1024                     # yat_gemma_attn_fwd's bound on one prompt
 
 _NORMS = ("input_layernorm", "post_attention_layernorm", "pre_feedforward_layernorm", "post_feedforward_layernorm")
-
-
-def find_text_encoder_dirs(pretrained_pipe_path):
-    """(``<pipe>/text_encoder``, ``<pipe>/tokenizer``) when the first holds a config.json and the second a tokenizer.json,
-    else None."""
-    if not pretrained_pipe_path:
-        return None
-    te, tk = os.path.join(pretrained_pipe_path, "text_encoder"), os.path.join(pretrained_pipe_path, "tokenizer")
-    if os.path.isfile(os.path.join(te, "config.json")) and os.path.isfile(os.path.join(tk, "tokenizer.json")):
-        return te, tk
-    return None
 
 
 def rope_theta(cfg: dict) -> float:
@@ -86,25 +73,17 @@ def expected_keys(cfg: dict) -> dict:
     return want
 
 
+def _stored_key(k: str):
+    kk = k[len("model."):] if k.startswith("model.") else k
+    return None if kk.startswith("lm_head.") else kk
+
+
 def load_text_encoder_dir(te_dir: str):
     """A transformers Gemma-2 directory -> (config dict, {key without ``model.``: tensor}).  Reads ``model.safetensors`` or
     the shards of ``model.safetensors.index.json``; ``lm_head.*`` is ignored; a missing or unexpected key raises and names it."""
-    from safetensors import safe_open
     cfg = read_config(te_dir)
     validate_config(cfg)
-    index = os.path.join(te_dir, "model.safetensors.index.json")
-    if os.path.isfile(index):
-        with open(index) as f:
-            files = sorted(set(json.load(f)["weight_map"].values()))
-    else:
-        files = ["model.safetensors"]
-    sd = {}
-    for name in files:
-        with safe_open(os.path.join(te_dir, name), framework="pt") as f:
-            for k in f.keys():
-                kk = k[len("model."):] if k.startswith("model.") else k
-                if not kk.startswith("lm_head."):
-                    sd[kk] = f.get_tensor(k)
+    sd = read_text_encoder_tensors(te_dir, _stored_key)
     check_expected(expected_keys(cfg), sd, lambda k: True, "Gemma-2", "Gemma2EncoderHIP")
     return cfg, sd
 
@@ -117,13 +96,16 @@ def rope_tables(dh: int, theta: float, length: int, dtype=BF16):
     return emb.cos().to(dtype), emb.sin().to(dtype)
 
 
-class Gemma2EncoderHIP:
+class Gemma2EncoderHIP(TextEncoderHIP):
     """Host side of the Gemma-2 encoder: packed weights on the device and the activation buffers of the largest call."""
+    model_type = "gemma2"
+    load_text_encoder_dir = staticmethod(load_text_encoder_dir)
+    EMPTY_HINT = "the tokenizer's template supplies BOS"
+    MAX_PROMPT_RULE = "min(sliding_window, max_position_embeddings, 1024)"
 
     def __init__(self, cfg: dict, sd: dict, device="cuda", softcap: bool = True):
         validate_config(cfg)
-        self.cfg = cfg
-        self.device = torch.device(device)
+        super().__init__(cfg, device)
         self.H, self.I, self.dh = int(cfg["hidden_size"]), int(cfg["intermediate_size"]), int(cfg["head_dim"])
         self.Hq, self.Hkv = int(cfg["num_attention_heads"]), int(cfg["num_key_value_heads"])
         self.L = int(cfg["num_hidden_layers"])
@@ -134,9 +116,7 @@ class Gemma2EncoderHIP:
         self.max_prompt = min(int(cfg.get("sliding_window") or MAX_PROMPT), int(cfg.get("max_position_embeddings") or MAX_PROMPT),
                               MAX_PROMPT)
         self.embed_scale = float(torch.tensor(self.H ** 0.5).to(BF16))          # embed_scale.to(weight.dtype)
-
-        def dev(t):
-            return t.to(self.device, BF16).contiguous()
+        dev = self.dev
         self.embed = dev(sd["embed_tokens.weight"])
         self.norm = dev(sd["norm.weight"])
         self.layers = []
@@ -151,12 +131,6 @@ class Gemma2EncoderHIP:
                 **{n: dev(sd[p + n + ".weight"]) for n in _NORMS}})
         cos, sin = rope_tables(self.dh, rope_theta(cfg), self.max_prompt)
         self.cos, self.sin = cos.to(self.device), sin.to(self.device)
-        self._bufs = None
-
-    @classmethod
-    def from_pretrained(cls, te_dir: str, device="cuda", softcap: bool = True):
-        cfg, sd = load_text_encoder_dir(te_dir)
-        return cls(cfg, sd, device, softcap)
 
     def describe(self) -> str:
         cap = self.cfg.get("attn_logit_softcapping")
@@ -165,55 +139,15 @@ class Gemma2EncoderHIP:
                 f"attention logits NOT soft-capped (config: {cap}; the form transformers' SDPA attention computes)")
         return f"Gemma-2 text encoder on HIP: {self.L} layers, hidden {self.H}, {self.Hq}/{self.Hkv} heads of {self.dh}; {form}"
 
-    def free(self) -> None:
-        """Drop the weights and buffers (the trainer's validate() after its prompts are encoded)."""
-        self.embed = self.norm = self.layers = self.cos = self.sin = self._bufs = None
+    def _buffer_widths(self):
+        return {"h": self.H, "n": self.H, "qkv": (self.Hq + 2 * self.Hkv) * self.dh, "a": self.Hq * self.dh, "gu": 2 * self.I,
+                "act": self.I}
 
-    def _buffers(self, rows: int):
-        if self._bufs is not None and self._bufs[0] >= rows:
-            return self._bufs[1]
-        self._bufs = None
-        cap = (rows + 63) // 64 * 64
-
-        def e(n):
-            return torch.empty(cap, n, dtype=BF16, device=self.device)
-        bufs = {"h": e(self.H), "n": e(self.H), "qkv": e((self.Hq + 2 * self.Hkv) * self.dh), "a": e(self.Hq * self.dh),
-                "gu": e(2 * self.I), "act": e(self.I)}
-        self._bufs = (cap, bufs)
-        return bufs
-
-    @torch.no_grad()
-    def encode(self, prompts, max_batch=None):
-        """``prompts``: a list of 1-D integer id tensors -> a list of ``[L_i, hidden]`` bf16 tensors on the device."""
-        if self.layers is None:
-            raise RuntimeError("the encoder's weights were freed")
-        prompts = [torch.as_tensor(p).reshape(-1).to("cpu", torch.int64) for p in prompts]
-        vocab = self.embed.shape[0]
-        for p in prompts:
-            if p.numel() == 0:
-                raise ValueError("an empty id sequence cannot be encoded (the tokenizer's template supplies BOS)")
-            if p.numel() > self.max_prompt:
-                raise NotImplementedError(f"a prompt of {p.numel()} tokens is beyond the {self.max_prompt} this encoder is built "
-                                          "for (min(sliding_window, max_position_embeddings, 1024))")
-            if int(p.min()) < 0 or int(p.max()) >= vocab:
-                raise ValueError(f"token id outside the vocabulary [0, {vocab})")
-        step = int(max_batch) if max_batch else len(prompts)
-        out = []
-        for i in range(0, len(prompts), max(step, 1)):
-            out += self._encode_chunk(prompts[i:i + step])
-        return out
-
-    def _encode_chunk(self, prompts):
+    def _forward(self, pack, bufs, y):
         from . import ops
-        lens = [p.numel() for p in prompts]
-        rows, B = sum(lens), len(prompts)
-        off = torch.zeros(B + 1, dtype=torch.int64)
-        off[1:] = torch.tensor(lens).cumsum(0)
-        ids = torch.cat(prompts).to(torch.int32).to(self.device)
+        ids, off_d, lens, rows, B = pack.ids, pack.off_d, pack.lens, pack.rows, len(pack.lens)
         pos = torch.cat([torch.arange(n, dtype=torch.int32) for n in lens]).to(self.device)
-        off_d = off.to(torch.int32).to(self.device)
-        bufs = self._buffers(rows)
-        h, n, qkv, a, gu, act = (bufs[k][:rows] for k in ("h", "n", "qkv", "a", "gu", "act"))
+        h, n, qkv, a, gu, act = (bufs[k] for k in ("h", "n", "qkv", "a", "gu", "act"))
         H, I, dh, Hq, Hkv = self.H, self.I, self.dh, self.Hq, self.Hkv
         ops.embed_rows(ids, self.embed, self.embed_scale, h)
         for w in self.layers:
@@ -228,6 +162,4 @@ class Gemma2EncoderHIP:
             ops.geglu(gu, I, act)
             ops.gemm(act, w["down"], n, M=rows, N=H, K=I)
             ops.gemma_rmsnorm(n, w["post_feedforward_layernorm"], h, self.eps, residual=h)
-        y = torch.empty(rows, H, dtype=BF16, device=self.device)
         ops.gemma_rmsnorm(h, self.norm, y, self.eps)
-        return [y[int(off[b]):int(off[b + 1])] for b in range(B)]

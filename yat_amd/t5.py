@@ -19,30 +19,17 @@ The relative-position bias exists in block 0 only and is shared by all blocks; `
 """
 from __future__ import annotations
 
-import json
 import math
-import os
 
 import torch
 
+from .text_common import TextEncoderHIP, read_text_encoder_tensors
 from .vae_common import BF16, check_expected, read_config
 
 MAX_PROMPT = 512                      # yat_t5_attn_fwd's bound on one prompt
 
 _REL = "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"
 _EMBED = ("shared.weight", "encoder.embed_tokens.weight")
-
-
-def find_t5_dirs(pretrained_pipe_path):
-    """(``<pipe>/text_encoder``, ``<pipe>/tokenizer``) when the first holds a config.json and the second a tokenizer.json or a
-    spiece.model, else None."""
-    if not pretrained_pipe_path:
-        return None
-    te, tk = os.path.join(pretrained_pipe_path, "text_encoder"), os.path.join(pretrained_pipe_path, "tokenizer")
-    if os.path.isfile(os.path.join(te, "config.json")) and any(os.path.isfile(os.path.join(tk, n))
-                                                               for n in ("tokenizer.json", "spiece.model")):
-        return te, tk
-    return None
 
 
 def validate_config(cfg: dict) -> None:
@@ -87,20 +74,9 @@ def load_text_encoder_dir(te_dir: str):
     ``encoder.embed_tokens.weight`` or as both (then they must be equal); it comes back as ``shared.weight``.  Stored dtypes
     vary (transformers keeps ``wo`` in fp32 for some loads): everything is cast to bf16, as ``pipe.to(torch.bfloat16)`` does
     (train_pixart_sigma.py:52-54).  A missing or unexpected key raises and names it."""
-    from safetensors import safe_open
     cfg = read_config(te_dir)
     validate_config(cfg)
-    index = os.path.join(te_dir, "model.safetensors.index.json")
-    if os.path.isfile(index):
-        with open(index) as f:
-            files = sorted(set(json.load(f)["weight_map"].values()))
-    else:
-        files = ["model.safetensors"]
-    sd = {}
-    for name in files:
-        with safe_open(os.path.join(te_dir, name), framework="pt") as f:
-            for k in f.keys():
-                sd[k] = f.get_tensor(k)
+    sd = read_text_encoder_tensors(te_dir)
     a, b = (sd.pop(k, None) for k in _EMBED)
     if a is not None and b is not None and not (a.shape == b.shape and torch.equal(a.float(), b.float())):
         raise ValueError("T5: shared.weight and encoder.embed_tokens.weight are tied but the checkpoint stores them unequal")
@@ -132,14 +108,16 @@ def relative_bias_table(weight, num_buckets, max_distance, max_len):
     return torch.nn.functional.embedding(bucket, weight).t().to(BF16).contiguous()
 
 
-class T5EncoderHIP:
+class T5EncoderHIP(TextEncoderHIP):
     """Host side of the T5 encoder: packed weights on the device and the activation buffers of the largest call."""
     model_type = "t5"
+    load_text_encoder_dir = staticmethod(load_text_encoder_dir)
+    EMPTY_HINT = "T5's tokenizer always appends </s>"
+    MAX_PROMPT_RULE = "min(512, n_positions)"
 
     def __init__(self, cfg: dict, sd: dict, device="cuda"):
         validate_config(cfg)
-        self.cfg = cfg
-        self.device = torch.device(device)
+        super().__init__(cfg, device)
         self.d_model, self.d_ff, self.dh = int(cfg["d_model"]), int(cfg["d_ff"]), int(cfg["d_kv"])
         self.heads, self.L = int(cfg["num_heads"]), int(cfg["num_layers"])
         self.H = self.d_model                                      # the width of an embedding row, as Gemma2EncoderHIP.H
@@ -147,9 +125,7 @@ class T5EncoderHIP:
         self.num_buckets = int(cfg.get("relative_attention_num_buckets", 32))
         self.max_distance = int(cfg.get("relative_attention_max_distance", 128))
         self.max_prompt = min(MAX_PROMPT, int(cfg.get("n_positions") or MAX_PROMPT))
-
-        def dev(t):
-            return t.to(self.device, BF16).contiguous()
+        dev = self.dev
         self.embed = dev(sd["shared.weight"] if "shared.weight" in sd else sd["encoder.embed_tokens.weight"])
         self.norm = dev(sd["encoder.final_layer_norm.weight"])
         self.rel_weight = dev(sd[_REL])
@@ -165,12 +141,6 @@ class T5EncoderHIP:
                 "ln0": dev(sd[p + "layer.0.layer_norm.weight"]),
                 "ln1": dev(sd[p + "layer.1.layer_norm.weight"])})
         self._tables = {}
-        self._bufs = None
-
-    @classmethod
-    def from_pretrained(cls, te_dir: str, device="cuda"):
-        cfg, sd = load_text_encoder_dir(te_dir)
-        return cls(cfg, sd, device)
 
     def describe(self) -> str:
         return (f"T5 v1.1 text encoder on HIP: {self.L} blocks, d_model {self.d_model}, {self.heads} heads of {self.dh}, d_ff "
@@ -178,8 +148,7 @@ class T5EncoderHIP:
                 "bidirectional attention, gated GELU rounded once")
 
     def free(self) -> None:
-        """Drop the weights and buffers (the trainer's validate() after its prompts are encoded)."""
-        self.embed = self.norm = self.rel_weight = self.layers = self._bufs = None
+        super().free()
         self._tables = {}
 
     def _table(self, max_len: int):
@@ -189,51 +158,15 @@ class T5EncoderHIP:
             self._tables = {n: relative_bias_table(self.rel_weight, self.num_buckets, self.max_distance, n)}
         return n, self._tables[n]
 
-    def _buffers(self, rows: int):
-        if self._bufs is not None and self._bufs[0] >= rows:
-            return self._bufs[1]
-        self._bufs = None
-        cap = (rows + 63) // 64 * 64
+    def _buffer_widths(self):
+        return {"h": self.d_model, "n": self.d_model, "s": self.d_model, "qkv": 3 * self.heads * self.dh,
+                "a": self.heads * self.dh, "wi": 2 * self.d_ff, "act": self.d_ff}
 
-        def e(n):
-            return torch.empty(cap, n, dtype=BF16, device=self.device)
-        bufs = {"h": e(self.d_model), "n": e(self.d_model), "s": e(self.d_model), "qkv": e(3 * self.heads * self.dh),
-                "a": e(self.heads * self.dh), "wi": e(2 * self.d_ff), "act": e(self.d_ff)}
-        self._bufs = (cap, bufs)
-        return bufs
-
-    @torch.no_grad()
-    def encode(self, prompts, max_batch=None):
-        """``prompts``: a list of 1-D integer id tensors -> a list of ``[L_i, d_model]`` bf16 tensors on the device."""
-        if self.layers is None:
-            raise RuntimeError("the encoder's weights were freed")
-        prompts = [torch.as_tensor(p).reshape(-1).to("cpu", torch.int64) for p in prompts]
-        vocab = self.embed.shape[0]
-        for p in prompts:
-            if p.numel() == 0:
-                raise ValueError("an empty id sequence cannot be encoded (T5's tokenizer always appends </s>)")
-            if p.numel() > self.max_prompt:
-                raise NotImplementedError(f"a prompt of {p.numel()} tokens is beyond the {self.max_prompt} this encoder is built "
-                                          "for (min(512, n_positions))")
-            if int(p.min()) < 0 or int(p.max()) >= vocab:
-                raise ValueError(f"token id outside the vocabulary [0, {vocab})")
-        step = int(max_batch) if max_batch else len(prompts)
-        out = []
-        for i in range(0, len(prompts), max(step, 1)):
-            out += self._encode_chunk(prompts[i:i + step])
-        return out
-
-    def _encode_chunk(self, prompts):
+    def _forward(self, pack, bufs, y):
         from . import ops
-        lens = [p.numel() for p in prompts]
-        rows, B = sum(lens), len(prompts)
-        off = torch.zeros(B + 1, dtype=torch.int64)
-        off[1:] = torch.tensor(lens).cumsum(0)
-        ids = torch.cat(prompts).to(torch.int32).to(self.device)
-        off_d = off.to(torch.int32).to(self.device)
-        max_len, table = self._table(max(lens))
-        bufs = self._buffers(rows)
-        h, n, s, qkv, a, wi, act = (bufs[k][:rows] for k in ("h", "n", "s", "qkv", "a", "wi", "act"))
+        ids, off_d, rows, B = pack.ids, pack.off_d, pack.rows, len(pack.lens)
+        max_len, table = self._table(max(pack.lens))
+        h, n, s, qkv, a, wi, act = (bufs[k] for k in ("h", "n", "s", "qkv", "a", "wi", "act"))
         D, F, dh, H = self.d_model, self.d_ff, self.dh, self.heads
         ops.embed_rows(ids, self.embed, 1.0, h)
         for i, w in enumerate(self.layers):
@@ -248,6 +181,4 @@ class T5EncoderHIP:
             ops.gemm(n, w["wi"], wi, M=rows, N=2 * F, K=D)
             ops.geglu(wi, F, act)
             ops.gemm(act, w["wo"], s, M=rows, N=D, K=F)
-        y = torch.empty(rows, D, dtype=BF16, device=self.device)
         ops.t5_rmsnorm(s, self.norm, y, self.eps, residual=h)
-        return [y[int(off[b]):int(off[b + 1])] for b in range(B)]
