@@ -631,6 +631,45 @@ int yat_t5_attn_fwd(int B, int rows, int H, int dh, int max_len, const void* qkv
                     const void* bias_rel, const void* row_offsets, void* out, int ldo, yat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * CLIP text encoder (transformers CLIPTextModelWithProjection, forward only, bf16): CLIP-L (`text_encoder`) and OpenCLIP
+ * bigG (`text_encoder_2`) of the SD3.5 pipe -- pipe.encode_prompt train_sd35.py:79-92 (training captions), :113-118
+ * (validation prompts).  Packed as the two blocks above: prompt b is the row range [row_offsets[b], row_offsets[b + 1]).
+ * The model is causal, so a row depends on the earlier rows of its own prompt only and a prefix encodes exactly; SD3 still
+ * feeds all 77 ids because the pad rows are part of prompt_embeds.  q_proj|k_proj|v_proj, out_proj, fc1 and fc2 run on
+ * yat_gemm_bf16_ex with its bias epilogue (yat_amd/clip.py): each linear rounds once, after the bias, as the bf16 module
+ * does.  Every pointer below is 16-byte aligned unless it holds int32.
+ *
+ * yat_clip_embed: CLIPTextEmbeddings: out[r, :] = bf16(token_table[ids[r], :] + pos_table[positions[r], :]), the sum in fp32,
+ *   ONE rounding (the bf16 module's add).  ids, positions: int32 [rows] on the device, positions[r] = the index of row r inside
+ *   its own prompt; token_table: [vocab, D]; pos_table: [npos, D]; D % 8 == 0.  The caller rejects an id outside [0, vocab) or
+ *   a position outside [0, npos) before the call; the kernel never gathers through one (such a row is written as zeros).
+ * yat_clip_layernorm: nn.LayerNorm with weight and bias: y = bf16((x - mean) * rstd * w + b), mean, variance and the affine in
+ *   fp32, ONE rounding; rstd = 1 / sqrt(var + eps) with var = mean((x - mean)^2) (a second pass over the row, not
+ *   E[x^2] - mean^2).  residual != NULL: the block's residual add comes first -- sum_out = bf16(residual + x) is stored and y
+ *   is the norm of that stored sum (the pre-norm order h = h + sublayer(norm(h)), then the next norm reads h: one pass does
+ *   both).  x, residual, sum_out, y: [M, D], D % 8 == 0; sum_out may alias residual (not x, not y) and is not touched when
+ *   residual == NULL.
+ * yat_clip_act: y[i] = bf16(act(x[i])) on n contiguous elements, n % 8 == 0, act evaluated in fp32, ONE rounding; y may be
+ *   x.  kind 1: QuickGELUActivation x * sigmoid(1.702 x) (CLIP-L); kind 2: GELUActivation 0.5 x (1 + erf(x / sqrt 2)) (bigG).
+ *   It follows fc1 + bias (rounded by the GEMM), which gives the module's two roundings; the bf16 module's quick-GELU
+ *   rounds 1.702 x and the sigmoid as well, so this one is no further from the fp32 value.
+ * yat_clip_attn_fwd: eager_attention_forward of CLIPAttention over packed prompts: causal, s = q k^T * scale, keys j > i
+ *   dropped, softmax and accumulation in fp32 (the probabilities rounded to bf16 for the P V product; the row sum adds the
+ *   same rounded values), out = bf16 [rows, H * dh] with row stride ldo.  q, k, v are the column blocks of qkv [rows, ld]
+ *   that start at columns q_off, k_off, v_off.  row_offsets: int32 [B + 1] on the device, ascending, inside [0, rows]; no
+ *   prompt is longer than max_len.  A query tile walks the key tiles up to its own and no further; a row past a prompt's end
+ *   is never read as data.  YAT_EINVAL without a launch: dh != 64, max_len > 512, H < 1, scale <= 0, an offset or stride
+ *   that is not a multiple of 8.
+ * ------------------------------------------------------------------------------------------ */
+int yat_clip_embed(int rows, int D, int vocab, int npos, const void* ids, const void* positions, const void* token_table,
+                   const void* pos_table, void* out, yat_stream_t stream);
+int yat_clip_layernorm(int M, int D, float eps, const void* x, const void* w, const void* b, const void* residual,
+                       void* sum_out, void* y, yat_stream_t stream);
+int yat_clip_act(int64_t n, int kind, const void* x, void* y, yat_stream_t stream);
+int yat_clip_attn_fwd(int B, int rows, int H, int dh, int max_len, const void* qkv, int ld, int q_off, int k_off, int v_off,
+                      float scale, const void* row_offsets, void* out, int ldo, yat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * launch plans: replay a recorded sequence of entry-point calls and stream / event operations in ONE call.
  * A training step over the same buffers issues the same ~900 launches and ~500 stream / event operations every time
  * (yat_amd/flat.py records them); replaying the list from C costs ~1 us per entry instead of a host-language call each.

@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
 """Side measurement (not a gate): a text encoder at its real shape on the HIP encoder with random bf16 weights made on the
 device.  ``--kind gemma2``: SANA's, Gemma-2-2B's shape (26 layers, 2304 wide, 8 / 4 heads of 256, MLP 9216, vocabulary 256000);
-``--kind t5``: PixArt-Sigma's, T5-XXL's encoder shape (24 blocks, d_model 4096, 64 heads of 64, d_ff 10240, vocabulary 32128).
-B = 1 and B = 8 prompts of 300 tokens, timed with HIP events after warm-up; prints one JSON line:
+``--kind t5``: PixArt-Sigma's, T5-XXL's encoder shape (24 blocks, d_model 4096, 64 heads of 64, d_ff 10240, vocabulary 32128);
+``--kind clip``: SD3.5's two CLIP text encoders, one after the other in one line (``shapes``): CLIP-L's shape (12 blocks, 768
+wide, 12 heads of 64, MLP 3072, quick-GELU) and OpenCLIP bigG's (32 blocks, 1280 wide, 20 heads of 64, MLP 5120, GELU), both
+with the 49408-token vocabulary, at prompts of 77 tokens.
+B = 1 and B = 8 prompts of 300 tokens (CLIP: 77), timed with HIP events after warm-up; prints one JSON line:
 
     per batch size: ms per call (median; every repeat listed), tokens per second, the share of each kernel kind in an
     instrumented pass (an event pair around every launch; attention's share is ``share.gemma_attn_fwd`` / ``share.t5_attn_fwd``),
     the GEMM and attention rates that pass reached, and both floors: the weight bytes at the HBM rate measured in this run (a
     device-to-device copy of 1 GiB, read + write counted) and the GEMM FLOPs at the project's measured 1120 TFLOP/s.
 
-    python scripts/bench_text_encoder.py [--kind gemma2|t5] [--layers N] [--tokens 300] [--batches 1 8] [--warmup 3] [--repeats 10]
+    python scripts/bench_text_encoder.py [--kind gemma2|t5|clip] [--layers N] [--tokens 300] [--batches 1 8] [--warmup 3] [--repeats 10]
 """
 import argparse
 import json
@@ -20,7 +23,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from yat_amd import gemma2, t5  # noqa: E402
+from yat_amd import clip, gemma2, t5  # noqa: E402
 from vae_bench_common import instrumented, timed  # noqa: E402
 
 BF = torch.bfloat16
@@ -38,6 +41,29 @@ def t5_xxl(layers):
     return dict(architectures=["T5EncoderModel"], model_type="t5", d_model=4096, num_layers=layers, num_heads=64, d_kv=64,
                 d_ff=10240, vocab_size=32128, layer_norm_epsilon=1e-6, relative_attention_num_buckets=32,
                 relative_attention_max_distance=128, feed_forward_proj="gated-gelu", is_encoder_decoder=False)
+
+
+def clip_shape(hidden, heads, mlp, act, projection):
+    def config(layers):
+        return dict(architectures=["CLIPTextModelWithProjection"], model_type="clip_text_model", hidden_size=hidden,
+                    num_hidden_layers=layers, num_attention_heads=heads, intermediate_size=mlp, hidden_act=act,
+                    projection_dim=projection, max_position_embeddings=77, vocab_size=49408, layer_norm_eps=1e-5, eos_token_id=2)
+    return config
+
+
+def clip_std(k, shape):
+    """(mean, std) of one CLIP weight: norm weights around 1, biases small, matrices at the fan-in scale."""
+    if len(shape) == 1:
+        return (1.0, 0.1) if "layer_norm" in k and k.endswith(".weight") else (0.0, 0.1)
+    return 0.0, 1.0 if "embedding" in k else shape[1] ** -0.5
+
+
+def clip_kind(metric, layers, config):
+    return dict(
+        metric=metric, layers=layers, config=config, module=clip, cls=clip.CLIPTextEncoderHIP, std=clip_std, tokens=77,
+        kinds=("gemm", "clip_attn_fwd", "clip_layernorm", "clip_act", "clip_embed"), attn="clip_attn_fwd",
+        params=lambda e: 4 * e.hidden * e.hidden + 2 * e.ff * e.hidden,
+        heads=lambda e: e.heads, pairs=lambda n: n * (n + 1) / 2, header=lambda e: {"hidden_act": e.act})
 
 
 def gemma2_std(k, shape):
@@ -70,7 +96,10 @@ KIND = {
         kinds=("gemm", "t5_attn_fwd", "t5_rmsnorm", "geglu", "embed_rows"), attn="t5_attn_fwd",
         params=lambda e: 4 * e.heads * e.dh * e.d_model + 3 * e.d_ff * e.d_model,
         heads=lambda e: e.heads, pairs=lambda n: n * n, header=lambda e: {}),
+    "clip_l": clip_kind("clip_l_encode_ms", 12, clip_shape(768, 12, 3072, "quick_gelu", 768)),
+    "clip_g": clip_kind("clip_g_encode_ms", 32, clip_shape(1280, 20, 5120, "gelu", 1280)),
 }
+GROUPS = {"clip": ("clip_l", "clip_g")}                       # a --kind that runs several shapes into one line
 
 
 def device_weights(kind, cfg, seed=0):
@@ -95,22 +124,19 @@ def hbm_rate(repeats=10):
     return 2.0 * src.numel() / (ms * 1e-3)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--kind", choices=sorted(KIND), default="gemma2")
-    ap.add_argument("--layers", type=int, help="default: the model's own (26 / 24)")
-    ap.add_argument("--tokens", type=int, default=300)
-    ap.add_argument("--batches", type=int, nargs="+", default=[1, 8])
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=10)
-    a = ap.parse_args()
-    kind = KIND[a.kind]
+def flat(res):
+    """The tensors of an encode() result: rows per prompt, or CLIP's (rows, pooled) pairs."""
+    return [t for r in res for t in (r if isinstance(r, (tuple, list)) else (r,))]
+
+
+def measure(kind, a, rate):
     layers = a.layers or kind["layers"]
+    tokens = a.tokens or kind.get("tokens", 300)
+    a = argparse.Namespace(**{**vars(a), "tokens": tokens})
     cfg = kind["config"](layers)
     enc = kind["cls"](cfg, device_weights(kind, cfg), device="cuda")
     layer_params = kind["params"](enc)
     weight_bytes = 2.0 * layer_params * layers
-    rate = hbm_rate()
     out = {"metric": kind["metric"], "layers": layers, "tokens_per_prompt": a.tokens, **kind["header"](enc),
            "hbm_bytes_per_s_measured": round(rate / 1e9, 1) * 1e9, "weight_gb": round(weight_bytes / 1e9, 3),
            "gemm_tflops_assumed": GEMM_TFLOPS, "batches": []}
@@ -138,8 +164,25 @@ def main():
             "share": {k: round(v / total, 3) for k, v in kind_ms.items()},
             "gemm_tflops_reached": round(gemm_flops / 1e9 / max(kind_ms["gemm"], 1e-9), 1),
             "attn_tflops_reached": round(attn_flops / 1e9 / max(kind_ms[kind["attn"]], 1e-9), 1),
-            "finite": bool(all(torch.isfinite(r.float()).all() for r in res))})
-    print(json.dumps(out))
+            "finite": bool(all(torch.isfinite(r.float()).all() for r in flat(res)))})
+    enc.free()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", choices=sorted(set(KIND) - {k for g in GROUPS.values() for k in g} | set(GROUPS)), default="gemma2")
+    ap.add_argument("--layers", type=int, help="default: the model's own (26 / 24; CLIP: 12 and 32)")
+    ap.add_argument("--tokens", type=int, help="default: 300 (CLIP: 77)")
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 8])
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=10)
+    a = ap.parse_args()
+    rate = hbm_rate()
+    if a.kind in GROUPS:
+        print(json.dumps({"metric": a.kind + "_encode_ms", "shapes": [measure(KIND[k], a, rate) for k in GROUPS[a.kind]]}))
+    else:
+        print(json.dumps(measure(KIND[a.kind], a, rate)))
 
 
 if __name__ == "__main__":

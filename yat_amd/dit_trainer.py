@@ -23,7 +23,7 @@ class DiTTrainer(Model):
     apply_shift = None              # ``encode(images, apply_shift=...)``; None: the encoder takes no such argument (DC-AE)
     validation_seed_on_device = True
     step_generator = False          # hand the trainer's per-step generator to the recipe (else: the global RNG streams)
-    text_encoder_kind = None        # "gemma2" / "t5": the pipe's text encoder, built at first use (yat_amd/encode_prompts.py);
+    text_encoder_kind = None        # "gemma2" / "t5" / "clip_text_model": the pipe's text encoder, built at first use (yat_amd/encode_prompts.py);
     text_encoder_noun = None        # None: this trainer has no text side and trains from cached embeddings only
 
     def __init__(self, params: TrainingParameters, accelerator=None, config=None):
@@ -83,14 +83,19 @@ class DiTTrainer(Model):
         if find_text_dirs(pipe, self.text_encoder_kind) is None:
             want = os.path.join(pipe or "<pretrained_pipe_path>", "text_encoder")
             raise NotImplementedError(f"text encoding needs the {self.text_encoder_noun} encoder in {want!r} (config.json + "
-                                      "safetensors) and the tokenizer beside it; without them, train from cached-feature shards")
+                                      "safetensors) and the tokenizer beside it; without them text encoding is outside the hot-path "
+                                      "scope: train from cached-feature shards")
         enc = load_encoder(pipe, device=self.accelerator.device)
-        want = self.model.config.caption_channels
-        if enc[0].H != want:
-            raise ValueError(f"the text encoder's hidden size {enc[0].H} is not the transformer's caption_channels {want}")
+        self.check_text_encoder_width(enc[0])
         print(enc[0].describe())
         self.text_encoder = enc
         return enc
+
+    def check_text_encoder_width(self, encoder):
+        """ValueError when the encoder's rows do not fit the transformer."""
+        want = self.model.config.caption_channels
+        if encoder.H != want:
+            raise ValueError(f"the text encoder's hidden size {encoder.H} is not the transformer's caption_channels {want}")
 
     def extract_embeddings(self, captions):
         from .encode_prompts import extract_embeddings
@@ -101,7 +106,8 @@ class DiTTrainer(Model):
         emb = super().load_empty_embeddings()
         if self.text_encoder_kind is None:
             return emb
-        return [e.cpu() for e in emb]                                  # the step stages its embeddings from the host
+        # the step stages its embeddings from the host (SD3.5: a (prompt, pooled) pair per sample)
+        return [tuple(t.cpu() for t in e) if isinstance(e, (tuple, list)) else e.cpu() for e in emb]
 
     def encode_validation_prompts(self):
         """The first third of the reference's ``validate()`` for a trainer that has a text encoder: the entries of
@@ -124,7 +130,8 @@ class DiTTrainer(Model):
         """The middle third of the reference's ``validate()``: 20 sampling steps with CFG 5.0 over the HIP transformer,
         generator seeded 42.  The prompt embeddings come from a cached file (``validation_embeds.pt`` next to the shards or in
         the cwd: a list of tuples as ``pipe.encode_prompt`` returns them) or, without one, from ``encode_validation_prompts``
-        (SANA and PixArt-Sigma with a text encoder in the pipe directory; SD3.5's text encoders are outside this build's scope), and the result is the latents (``output_type='latent'``), stored under models/<step>/ with a three-channel
+        (with the text encoders in the pipe directory: SANA's Gemma-2, PixArt-Sigma's T5, SD3.5's CLIP-L + OpenCLIP bigG + T5),
+        and the result is the latents (``output_type='latent'``), stored under models/<step>/ with a three-channel
         preview for the logger.  With a VAE in ``<pretrained_pipe_path>/vae`` the last third runs too: each latent is decoded
         on the HIP decoder (built at the first call; ``vae.decode(latent / scaling_factor)`` -> ``postprocess``), logged as
         ``validation/{idx}/{prompt}`` and written to models/<step>/validation_{idx}.png."""

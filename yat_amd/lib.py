@@ -128,6 +128,10 @@ SIGNATURES = {
     "yat_gemma_attn_fwd": (I, [I, I, I, I, I, I, F, F, P, I, I, I, I, P, P, I, P]),
     "yat_t5_rmsnorm": (I, [I, I, F, P, P, P, P, P, P]),
     "yat_t5_attn_fwd": (I, [I, I, I, I, I, P, I, I, I, I, P, P, P, I, P]),
+    "yat_clip_embed": (I, [I, I, I, I, P, P, P, P, P, P]),
+    "yat_clip_layernorm": (I, [I, I, F, P, P, P, P, P, P, P]),
+    "yat_clip_act": (I, [I64, I, P, P, P]),
+    "yat_clip_attn_fwd": (I, [I, I, I, I, I, P, I, I, I, I, F, P, P, I, P]),
     "yat_plan_op_id": (I, [C.c_char_p]),
     "yat_plan_replay": (I, [C.POINTER(PlanEntry), I, C.POINTER(I)]),
     "yat_comm_available": (I, []),

@@ -1006,3 +1006,66 @@ def t5_attn_fwd(qkv2d, row_offsets_i32, B, H, dh, max_len, bias_rel, out):
                                 _p(bias_rel), _p(row_offsets_i32), _p(out), out.stride(0), _stream())
     _l.check(rc, "yat_t5_attn_fwd")
     return out
+
+
+# ---------------------------------------------------------------------------------- CLIP text encoder (yat_amd/clip.py)
+CLIP_ACT = {"quick_gelu": 1, "gelu": 2}
+
+
+def clip_embed(ids_i32, pos_i32, token_table, pos_table, out):
+    """out[r] = bf16(token_table[ids[r]] + pos_table[pos[r]]) (include/yat_hip.h yat_clip_embed).  ``ids_i32`` / ``pos_i32``:
+    int32 [rows] on the device; an id or a position outside its table raises here (a host check) and is never gathered."""
+    _chk_bf16(token_table, pos_table, out)
+    for t in (ids_i32, pos_i32):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != ids_i32.numel():
+            raise TypeError("clip_embed wants contiguous 1-D int32 id and position tensors of one length")
+    (vocab, D), npos = token_table.shape, pos_table.shape[0]
+    if pos_table.shape[1] != D:
+        raise ValueError("clip_embed: the two tables must have one width")
+    lo, hi = int(ids_i32.min()), int(ids_i32.max())
+    if lo < 0 or hi >= vocab:
+        raise ValueError(f"token id {lo if lo < 0 else hi} is outside the vocabulary [0, {vocab})")
+    lo, hi = int(pos_i32.min()), int(pos_i32.max())
+    if lo < 0 or hi >= npos:
+        raise ValueError(f"position {lo if lo < 0 else hi} is outside the position table [0, {npos})")
+    rc = _lib().yat_clip_embed(ids_i32.numel(), D, vocab, npos, _p(ids_i32), _p(pos_i32), _p(token_table), _p(pos_table),
+                               _p(out), _stream())
+    _l.check(rc, "yat_clip_embed")
+    return out
+
+
+def clip_layernorm(x2d, w, b, y, eps=1e-5, residual=None, sum_out=None):
+    """nn.LayerNorm with weight and bias, one rounding; with ``residual``: ``sum_out`` = bf16(residual + x) is stored (default:
+    in place on ``residual``) and ``y`` is its norm (yat_clip_layernorm)."""
+    if residual is not None and sum_out is None:
+        sum_out = residual
+    _chk_bf16(x2d, w, b, y, residual, sum_out)
+    M, D = x2d.shape
+    rc = _lib().yat_clip_layernorm(M, D, float(eps), _p(x2d), _p(w), _p(b), _p(residual),
+                                   _p(sum_out if residual is not None else None), _p(y), _stream())
+    _l.check(rc, "yat_clip_layernorm")
+    return y
+
+
+def clip_act(x, kind, out=None):
+    """``kind`` "quick_gelu" (x * sigmoid(1.702 x)) or "gelu" (erf) on a contiguous bf16 tensor, one rounding; ``out``
+    defaults to ``x`` itself (yat_clip_act)."""
+    out = x if out is None else out
+    _chk_bf16(x, out)
+    if not x.is_contiguous() or not out.is_contiguous() or out.numel() != x.numel():
+        raise ValueError("clip_act wants contiguous tensors of one size")
+    rc = _lib().yat_clip_act(x.numel(), CLIP_ACT[kind], _p(x), _p(out), _stream())
+    _l.check(rc, "yat_clip_act")
+    return out
+
+
+def clip_attn_fwd(qkv2d, row_offsets_i32, B, H, dh, max_len, scale, out):
+    """Causal scaled attention over packed prompts (yat_clip_attn_fwd); qkv2d = [q | k | v] blocks, ``row_offsets_i32``: int32
+    [B + 1] on the device, ``max_len`` >= the longest prompt."""
+    _chk_bf16(qkv2d, out)
+    if row_offsets_i32.dtype != torch.int32 or row_offsets_i32.numel() != B + 1:
+        raise ValueError("clip_attn_fwd: row_offsets must be int32 [B + 1]")
+    rc = _lib().yat_clip_attn_fwd(B, qkv2d.shape[0], H, dh, int(max_len), _p(qkv2d), qkv2d.stride(0), 0, H * dh, 2 * H * dh,
+                                  float(scale), _p(row_offsets_i32), _p(out), out.stride(0), _stream())
+    _l.check(rc, "yat_clip_attn_fwd")
+    return out
