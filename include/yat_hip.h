@@ -504,6 +504,25 @@ int yat_dcae_conv3x3_mean(int B, int H, int W, int Cin, int Cout, const void* x,
 int yat_dcae_image_from_uint8(int64_t npix, const void* x, const void* table, void* out, yat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * Image ingest: Pillow's antialiased bilinear resize of a packed uint8 RGB image, bit for bit --
+ *   img.resize((tw, th), Image.BILINEAR), what torchvision's Resize((th, tw)) does to a PIL image   bucket_sampler.py:324-398
+ * src: [H, W, 3] uint8, contiguous (3-byte pixels: no alignment is assumed); dst: [th, tw, 3] uint8, typically one slot of a
+ * [B, th, tw, 3] batch.  No byte outside src[0 .. H*W*3) is read and none outside dst[0 .. th*tw*3) is written.
+ * tables: one packed int32 block on the device, built by the host in doubles (yat_amd/image.py resample_tables):
+ *     [ tw x (xmin, n) | tw x ksize_h coefficients | th x (ymin, n) | th x ksize_v coefficients ]
+ * per axis ksize = ceil(max(in / out, 1)) * 2 + 1, coefficients in 22-bit fixed point; an axis whose size does not change
+ * has ksize 0 and no entries (tables may be NULL when both are 0: the image is copied).  ksize_h / ksize_v must be the
+ * values that formula gives.  H*W*3 and th*tw*3 must be < 2^31.
+ * yat_image_resize_plan (pure host code): 1 = one launch, a workgroup runs both passes of a 16 x 64 output tile through
+ *   LDS; 2 = two launches through `workspace` (yat_image_resize_workspace_bytes = H*tw*3 bytes, < 2^31), taken when 16
+ *   output rows read more source rows than the LDS image holds; YAT_EINVAL for sizes the entry point refuses.
+ * ------------------------------------------------------------------------------------------ */
+int yat_image_resize_plan(int H, int W, int th, int tw);
+uint64_t yat_image_resize_workspace_bytes(int H, int W, int th, int tw);
+int yat_image_resize_u8(int H, int W, int th, int tw, int ksize_h, int ksize_v, const void* src, const void* tables,
+                        void* dst, void* workspace, yat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * AutoencoderKL decoder (diffusers AutoencoderKL, decoder only): the VAE decode of the PixArt-Sigma and SD3.5 validation
  * images,  vae.decode(latent / vae.config.scaling_factor) -> image_processor.postprocess   train_pixart_sigma.py:137-144,
  * train_sd35.py:150-156, with the VAE in bf16.  Activations are NHWC bf16; every call only enqueues work.  The 3x3 convs run

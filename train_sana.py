@@ -7,10 +7,13 @@ train_sana.py:221-237), driving the MI355X-native hot path.
 
 ``pretrained_model_path`` (or ``pretrained_pipe_path``/transformer) must be a LOCAL diffusers directory
 (config.json + diffusion_pytorch_model.safetensors); with neither present the 1.6B architecture is random-initialised
-(there is no network here).  The ``extract_features`` / ``compute_features`` loop is outside the hot-path scope: training
-consumes cached-feature shards (``python -m yat_amd.extract_latents`` makes their latents on the HIP DC-AE encoder, which
-``extract_latents`` also uses; ``python -m yat_amd.encode_prompts`` makes their prompt embeddings on the HIP Gemma-2 encoder,
-which ``extract_embeddings`` also uses).  With ``<pretrained_pipe_path>/text_encoder`` + ``/tokenizer`` present, CFG dropout
+(there is no network here).  Training consumes cached-feature shards (``python -m yat_amd.extract_latents`` makes their
+latents on the HIP DC-AE encoder, which ``extract_latents`` also uses; ``python -m yat_amd.encode_prompts`` makes their prompt
+embeddings on the HIP Gemma-2 encoder, which ``extract_embeddings`` also uses) or, with ``compute_features: true`` (plus
+``vae_max_batch_size`` / ``text_encoder_max_batch_size``) and ``<pretrained_pipe_path>/vae`` + ``/text_encoder`` +
+``/tokenizer`` present, raw WebDataset shards of ``*.jpg`` + ``*.txt`` as img2dataset writes them: each image is resized
+to its bucket by the Pillow-exact HIP resize and encoded on the fly (``BucketSamplerExtractFeatures``).  The
+``extract_features`` loop (R2 upload) is outside the hot-path scope.  With ``<pretrained_pipe_path>/text_encoder`` + ``/tokenizer`` present, CFG dropout
 needs no ``empty_embeds.pt`` and validation no ``validation_embeds.pt``; without them both come from those cached files.
 When ``<pretrained_pipe_path>/vae`` holds the DC-AE, validation decodes its latents to images on the HIP decoder
 (yat_amd/dcae.py).

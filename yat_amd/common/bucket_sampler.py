@@ -18,7 +18,8 @@ queue) while the training thread is inside C-ABI launches (ctypes drops the GIL)
 critical path.  A thread, not a process: nothing is re-executed or forked once the GPU is initialised, and the decoded CPU
 tensors are handed over by reference.  The collectives of the consensus stay on the training thread -- one thread per rank
 talks to the process group.  ``decode_ahead=0`` (or ``YAT_SAMPLER_THREAD=0``) decodes synchronously.
-Out of scope: R2/HTTP download, on-the-fly VAE/text encoding, Dreambooth, dual-GPU and REPA branches.
+On-the-fly VAE / text encoding from raw image + caption shards: ``BucketSamplerExtractFeatures`` below.
+Out of scope: R2/HTTP download, Dreambooth, dual-GPU and REPA branches.
 """
 from __future__ import annotations
 
@@ -32,7 +33,7 @@ from collections import deque
 import torch
 import torch.distributed as dist
 
-from .shards import iter_legacy_cache, read_shard
+from .shards import iter_legacy_cache, read_raw_shard, read_shard
 
 
 class Batch:
@@ -186,8 +187,101 @@ class BucketSampler:
                     self.process_element(next(stream))
                 continue
             items = [self.buckets[key].popleft() for _ in range(self.batch_size)]
-            batch = Batch()
-            batch.ratio = key
-            batch.vae_features = torch.stack([it[0] for it in items])       # :161-162
-            batch.embeddings = [it[1] for it in items]
-            yield batch
+            yield self.make_batch(key, items)
+
+    def make_batch(self, key, items):
+        batch = Batch()
+        batch.ratio = key
+        batch.vae_features = torch.stack([it[0] for it in items])       # :161-162
+        batch.embeddings = [it[1] for it in items]
+        return batch
+
+
+class BucketSamplerExtractFeatures(BucketSampler):
+    """``compute_features: true`` (trainer.py:182-199, bucket_sampler.py:324-398): train straight from raw WebDataset shards
+    of ``<key>.jpg`` + ``<key>.txt`` as img2dataset writes them.  Everything of the base class is kept -- the producer thread
+    with its ``close()`` / join, the seeded shard order, one MIN all-reduce consensus per batch -- and three things change:
+
+    * the producer thread reads tars and decodes images (``read_raw_shard``) and does nothing else: no GPU call leaves the
+      training thread.  A decoded photograph is megabytes (12 megapixels: 36 MB), not the ~100 KB of a cached sample, so the
+      bounded queue holds ``2 * batch_size`` samples instead of the base's ``16 * batch_size``, and the samples of a shard
+      are mixed through a seeded shuffle buffer of ``2 * batch_size`` instead of a shuffle of the whole decoded shard;
+    * ``process_element`` buckets by ``find_closest_ratio(h / w)`` over ``model.aspect_ratios`` (first minimum wins, the
+      function of ``yat_amd.extract_latents``) and resizes the image AT INGEST to the bucket's ``(th, tw)`` -- on the device
+      with ``device_resize=True`` (``yat_amd.image.resize_uint8``: one upload of the decoded image, the HIP kernel, the
+      result stays on the device), by Pillow otherwise; both give Pillow's bytes.  The bucket stores ``(resized [th, tw, 3]
+      uint8 tensor, caption)``.  Buckets are ``deque(maxlen=4 * batch_size)``: a bucket that the other ranks never fill
+      drops its oldest entry (the reference's is ``maxlen=batch_size``, bucket_sampler.py:149), so at most ``len(table) * 4 *
+      batch_size`` resized images are resident, ``th * tw * 3`` bytes each (1024 table: ~3 MB each);
+    * a yielded batch is stacked to ``[B, th, tw, 3]``, encoded in chunks of ``vae_max_batch_size`` through
+      ``model.extract_latents_uint8`` and its captions in chunks of ``text_encoder_max_batch_size`` through
+      ``model.extract_embeddings``, and handed over as the cached path hands it over: ``vae_features`` ``[B, C, h, w]`` bf16 and
+      ``embeddings`` a list of ``[L, C]`` tensors (SD3.5: ``(emb, pooled)`` pairs), all on the host, so the step's one-copy
+      staging and the recipes are untouched (keeping the features on the device is a later change).
+
+    The noise of an AutoencoderKL latent comes from a generator the sampler owns, on the accelerator's device, seeded
+    ``seed + process_index``: the same shards and seed give the same batches.
+    Out of scope: R2 / HTTP download, Dreambooth, dual-GPU and REPA."""
+
+    def __init__(self, shards, accelerator, batch_size, model, seed=0, local_paths=None, features_path=None,
+                 max_read_ahead=4096, decode_ahead=None, vae_max_batch_size=None, text_encoder_max_batch_size=None,
+                 device_resize=True):
+        super().__init__(shards, accelerator, batch_size, model=model, seed=seed, local_paths=local_paths,
+                         features_path=features_path, max_read_ahead=max_read_ahead, decode_ahead=decode_ahead)
+        if decode_ahead is None and self.decode_ahead > 0:
+            self.decode_ahead = 2 * batch_size
+        self.model = model
+        self.sizes = {float(k): (int(v[0]), int(v[1])) for k, v in model.aspect_ratios.items()}
+        self.buckets = {k: deque(maxlen=4 * batch_size) for k in self.keys}
+        self.vae_max_batch_size = int(vae_max_batch_size or batch_size)
+        self.text_encoder_max_batch_size = int(text_encoder_max_batch_size or batch_size)
+        self.device_resize = bool(device_resize)
+        self.generator = None
+
+    def _shard_stream(self):
+        rng = random.Random(self.seed + self.process_index)
+        held = []
+        while True:
+            order = list(self.paths)
+            rng.shuffle(order)
+            seen = 0
+            for p in order:
+                for sample in read_raw_shard(p):
+                    seen += 1
+                    held.append(sample)
+                    if len(held) > 2 * self.batch_size:
+                        yield held.pop(rng.randrange(len(held)))
+            if not seen:
+                raise FileNotFoundError(f"BucketSamplerExtractFeatures: no decodable image + caption sample in {self.paths}")
+
+    def process_element(self, elem):
+        from ..extract_latents import find_closest_ratio
+        from ..image import pillow_resize, resize_uint8
+        img = torch.from_numpy(elem["image"])
+        h, w = img.shape[:2]
+        key = float(find_closest_ratio(self.model.aspect_ratios, h / w))
+        th, tw = self.sizes[key]
+        if self.device_resize:
+            img = resize_uint8(img, th, tw, device=self.accelerator.device)
+        else:
+            img = pillow_resize(img, th, tw)
+        self.buckets[key].append((img, elem["caption"]))
+
+    def make_batch(self, key, items):
+        if self.generator is None:
+            self.generator = torch.Generator(device=self.accelerator.device).manual_seed(self.seed + self.process_index)
+        images = torch.stack([it[0] for it in items])
+        captions = [it[1] for it in items]
+        host = lambda e: tuple(t.cpu() for t in e) if isinstance(e, (tuple, list)) else e.cpu()      # noqa: E731
+        latents, embeddings = [], []
+        with torch.no_grad():
+            for i in range(0, len(items), self.vae_max_batch_size):
+                chunk = images[i:i + self.vae_max_batch_size]
+                latents.append(self.model.extract_latents_uint8(chunk, generator=self.generator).to(torch.bfloat16).cpu())
+            for i in range(0, len(items), self.text_encoder_max_batch_size):
+                embeddings += [host(e) for e in self.model.extract_embeddings(captions[i:i + self.text_encoder_max_batch_size])]
+        batch = Batch()
+        batch.ratio = key
+        batch.vae_features = torch.cat(latents)
+        batch.embeddings = embeddings
+        return batch

@@ -4,6 +4,7 @@ Wire format = what the reference's FeaturesExtractor writes (common/features_ext
 BucketSampler decodes (common/bucket_sampler.py:138-156): a POSIX tar whose members are grouped by key,
 ``<key>.ratio`` (ascii float), ``<key>.latent.pt`` (torch.save of the [C, h, w] bf16 latent) and ``<key>.emb.pt``
 (torch.save of the UNPADDED [L, C] bf16 text embedding -- only mask-true rows, train_sana.py:92-94).
+``read_raw_shard`` reads the other kind of shard with the same grouping: raw images + captions (``compute_features``).
 """
 from __future__ import annotations
 
@@ -66,6 +67,63 @@ def read_shard(path):
 
 def _complete(s):
     return "ratio" in s and "latent.pt" in s and "emb.pt" in s
+
+
+# ---- raw shards: images + captions --------------------------------------------------------------------------------------
+IMAGE_EXTENSIONS = ("jpg", "jpeg", "png")
+
+
+def read_raw_shard(path, report=print):
+    """Yield ``{__key__, image: [H, W, 3] uint8 contiguous array, caption: str}`` of a raw WebDataset tar as img2dataset writes
+    it (``<key>.jpg`` + ``<key>.txt`` [+ ``<key>.json``]), in tar order, with the grouping of ``read_shard``.  Of a sample's
+    members the ``jpg`` / ``jpeg`` / ``png`` one (any letter case) and the ``txt`` one are kept and the rest ignored; the image
+    is decoded with ``Image.open(...).convert("RGB")`` and the caption as UTF-8.  A sample with a member that does not decode
+    is dropped and counted, as is one that lacks either member; ``report`` gets one line per shard with the counts."""
+    import numpy as np
+    from PIL import Image
+    kept = dropped = 0
+
+    def finish(cur):
+        nonlocal kept, dropped
+        if cur.get("bad") or "image" not in cur or "caption" not in cur:
+            dropped += 1
+            return None
+        kept += 1
+        return {"__key__": cur["__key__"], "image": cur["image"], "caption": cur["caption"]}
+
+    cur_key, cur = None, {}
+    with tarfile.open(path, "r") as tar:
+        for m in tar:
+            if not m.isfile():
+                continue
+            base = m.name.split("/")[-1]
+            key, _, ext = base.partition(".")
+            key = m.name[: len(m.name) - len(base)] + key
+            if cur_key is not None and key != cur_key:
+                sample = finish(cur)
+                if sample is not None:
+                    yield sample
+                cur = {}
+            cur_key = key
+            cur["__key__"] = key
+            ext = ext.lower()
+            if ext not in IMAGE_EXTENSIONS and ext != "txt":
+                continue
+            data = tar.extractfile(m).read()
+            try:
+                if ext == "txt":
+                    cur["caption"] = data.decode("utf-8")
+                else:
+                    with Image.open(io.BytesIO(data)) as im:
+                        cur["image"] = np.array(im.convert("RGB"), dtype=np.uint8, order="C")
+            except Exception:       # noqa: BLE001 -- whatever the decoder raises (truncated file, bad header, bad UTF-8)
+                cur["bad"] = True
+        if cur_key is not None:
+            sample = finish(cur)
+            if sample is not None:
+                yield sample
+    if report is not None:
+        report(f"{path}: {kept} sample(s), {dropped} dropped (undecodable or incomplete)")
 
 
 # ---- legacy cache: one file per sample ------------------------------------------------------------------------------

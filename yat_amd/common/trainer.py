@@ -270,6 +270,16 @@ class Model:
     def extract_embeddings(self, captions):
         raise NotImplementedError
 
+    def extract_latents_uint8(self, images_u8, generator=None):
+        """``extract_latents`` of ``[B, H, W, 3]`` uint8 images as PIL hands them over (ToTensor -> Normalize(0.5, 0.5) on the
+        device); ``generator``: the noise of a sampling VAE."""
+        raise NotImplementedError
+
+    def check_feature_extractors(self):
+        """Raise what ``extract_latents`` / ``extract_embeddings`` would raise at the first batch, before any batch is read
+        (``compute_features: true``)."""
+        raise NotImplementedError("compute_features needs a trainer with a VAE encoder and a text encoder")
+
     def format_embeddings(self, embeds):
         pass
 
@@ -342,9 +352,17 @@ class Model:
                          use_ema=bool(getattr(p, "use_ema", False)), ema_decay=0.999, overlap_update=True)
 
     def make_sampler(self):
-        """Cached-feature sampler over this rank's shard range (the intended path of :165-181)."""
-        from .bucket_sampler import BucketSampler
+        """Cached-feature sampler over this rank's shard range (the intended path of :165-181); with ``compute_features: true``
+        the sampler that encodes raw image + caption shards on the fly (:182-199), over the same shard list -- a missing VAE
+        or text encoder directory is an error here, not at the first batch."""
+        from .bucket_sampler import BucketSampler, BucketSamplerExtractFeatures
         shards = [f"shard-{i:06d}.tar" for i in range(self.shard_index_begin, self.shard_index_end)]
+        if getattr(self.params, "compute_features", None):
+            self.check_feature_extractors()
+            return BucketSamplerExtractFeatures(shards, self.accelerator, self.params.batch_size, model=self,
+                                                seed=self.params.dataset_seed, local_paths=self.params.local_shard_paths,
+                                                vae_max_batch_size=getattr(self.params, "vae_max_batch_size", None),
+                                                text_encoder_max_batch_size=getattr(self.params, "text_encoder_max_batch_size", None))
         # a legacy per-sample cache (cache/{idx}.npy tuples written by the reference's common/cache.py) is used when
         # present and no shard list is configured
         legacy = "cache" if (not self.params.local_shard_paths and os.path.isdir("cache")

@@ -59,37 +59,65 @@ class DiTTrainer(Model):
         """One entry of ``validation_embeds.pt`` -> latents, through the model's sampler in ``yat_amd.sampler``."""
         raise NotImplementedError
 
-    def extract_latents(self, images):
+    def _vae_encoder(self):
+        """The VAE encoder, built once; NotImplementedError without ``<pretrained_pipe_path>/vae``."""
+        self._require_vae()
+        if self.vae_encoder is None:
+            self.vae_encoder = load_vae_encoder(self.vae_dir, device=self.accelerator.device)
+        return self.vae_encoder
+
+    def _require_vae(self):
         if self.vae_dir is None:
             want = os.path.join(self.params.pretrained_pipe_path or "<pretrained_pipe_path>", "vae")
             raise NotImplementedError(f"VAE encoding needs the {self.vae_noun} in {want!r} (config.json + safetensors); without "
                                       "it, train from cached-feature shards")
-        if self.vae_encoder is None:
-            self.vae_encoder = load_vae_encoder(self.vae_dir, device=self.accelerator.device)
+
+    def extract_latents(self, images):
+        enc = self._vae_encoder()
         if self.apply_shift is None:
-            return self.vae_encoder.encode(images)
-        return self.vae_encoder.encode(images, apply_shift=self.apply_shift)
+            return enc.encode(images)
+        return enc.encode(images, apply_shift=self.apply_shift)
+
+    def extract_latents_uint8(self, images_u8, generator=None):
+        """``[B, H, W, 3]`` uint8 -> what ``extract_latents`` gives for ToTensor -> Normalize(0.5, 0.5) of them; an AutoencoderKL
+        draws its sample's noise from ``generator``."""
+        enc = self._vae_encoder()
+        if self.apply_shift is None:
+            return enc.encode_uint8(images_u8)
+        return enc.encode_uint8(images_u8, apply_shift=self.apply_shift, generator=generator)
+
+    def check_feature_extractors(self):
+        self._require_vae()
+        self._require_text_dirs()
 
     def _text_encoder(self):
         """(encoder, tokenizer), built once from ``<pretrained_pipe_path>/text_encoder`` + ``/tokenizer``;
         NotImplementedError without the two directories (raised before the model or the device is looked at)."""
         if self.text_encoder_kind is None:
             raise NotImplementedError("text encoding is outside the hot-path scope; train from cached-feature shards")
-        from .encode_prompts import find_text_dirs, load_encoder
+        from .encode_prompts import load_encoder
         enc = getattr(self, "text_encoder", None)
         if enc is not None and enc[0].layers is not None:
             return enc
+        pipe = self._require_text_dirs()
+        enc = load_encoder(pipe, device=self.accelerator.device)
+        self.check_text_encoder_width(enc[0])
+        print(enc[0].describe())
+        self.text_encoder = enc
+        return enc
+
+    def _require_text_dirs(self):
+        """-> the pipe directory; NotImplementedError without its text encoder and tokenizer directories."""
+        if self.text_encoder_kind is None:
+            raise NotImplementedError("text encoding is outside the hot-path scope; train from cached-feature shards")
+        from .encode_prompts import find_text_dirs
         pipe = getattr(self.params, "pretrained_pipe_path", None)
         if find_text_dirs(pipe, self.text_encoder_kind) is None:
             want = os.path.join(pipe or "<pretrained_pipe_path>", "text_encoder")
             raise NotImplementedError(f"text encoding needs the {self.text_encoder_noun} encoder in {want!r} (config.json + "
                                       "safetensors) and the tokenizer beside it; without them text encoding is outside the hot-path "
                                       "scope: train from cached-feature shards")
-        enc = load_encoder(pipe, device=self.accelerator.device)
-        self.check_text_encoder_width(enc[0])
-        print(enc[0].describe())
-        self.text_encoder = enc
-        return enc
+        return pipe
 
     def check_text_encoder_width(self, encoder):
         """ValueError when the encoder's rows do not fit the transformer."""
@@ -112,7 +140,8 @@ class DiTTrainer(Model):
     def encode_validation_prompts(self):
         """The first third of the reference's ``validate()`` for a trainer that has a text encoder: the entries of
         ``validation_embeds.pt`` made from ``params.validation_prompts``, encoded once and kept for the later validations;
-        the encoder's weights are freed afterwards.  None without a text encoder."""
+        the encoder's weights are freed afterwards, unless ``compute_features`` keeps encoding captions with it.  None without
+        a text encoder."""
         kept = getattr(self, "validation_embeds", None)
         if kept is not None:
             return kept
@@ -122,8 +151,9 @@ class DiTTrainer(Model):
             return None
         from .encode_prompts import validation_embeddings
         self.validation_embeds = validation_embeddings(encoder, tokenizer, list(self.params.validation_prompts or []))
-        encoder.free()
-        self.text_encoder = None
+        if not getattr(self.params, "compute_features", None):     # (the extract-features sampler encodes every batch with it)
+            encoder.free()
+            self.text_encoder = None
         return self.validation_embeds
 
     def validate(self):

@@ -5,6 +5,7 @@ PixArt-Sigma, SD3.5).
 
     python -m yat_amd.extract_latents --vae PIPE/vae --resolution 1024 --out shard-000000.tar IMAGE...
     python -m yat_amd.extract_latents --vae PIPE/vae --resolution 1024 --seed 7 [--mode] [--no-shift] --out ... IMAGE...   # KL
+    python -m yat_amd.extract_latents --vae PIPE/vae --resolution 1024 --device-resize --out ... IMAGE...   # HIP resize, same bytes
 
 Per image: PIL decode to RGB -> bucket = ``find_closest_ratio(height / width)`` over the resolution's aspect table ->
 ``img.resize((tw, th), Image.BILINEAR)`` (what torchvision's ``Resize((th, tw))`` does to a PIL image) -> ToTensor /
@@ -74,24 +75,28 @@ def load_pooled(image_path: str):
     return pooled.reshape(-1).to(torch.bfloat16)
 
 
-def resized_uint8(image_path: str, table: dict):
-    """-> (ratio key, [th, tw, 3] uint8 tensor) of one image file."""
+def resized_uint8(image_path: str, table: dict, device=None):
+    """-> (ratio key, [th, tw, 3] uint8 tensor) of one image file.  ``device``: resize there with the Pillow-exact HIP kernel
+    (``yat_amd.image.resize_uint8``; the same bytes, left on the device) instead of with Pillow on the host."""
     import numpy as np
     from PIL import Image
     with Image.open(image_path) as im:
         img = im.convert("RGB")
     key, th, tw = bucket_for(table, img.height, img.width)
+    if device is not None:
+        from .image import resize_uint8
+        return key, resize_uint8(torch.from_numpy(np.array(img, dtype=np.uint8)), th, tw, device=device)
     img = img.resize((tw, th), Image.BILINEAR)
     return key, torch.from_numpy(np.array(img, dtype=np.uint8))
 
 
-def extract_samples(encoder, image_paths, table: dict, first_key: int = 0, **encode_options):
+def extract_samples(encoder, image_paths, table: dict, first_key: int = 0, resize_device=None, **encode_options):
     """Yield one shard sample per image; ``encoder`` needs ``encode_uint8([H, W, 3] uint8, **encode_options) -> [1, C, h,
     w]``."""
     for idx, path in enumerate(image_paths):
         emb = load_embedding(path)
         pooled = load_pooled(path)
-        key, u8 = resized_uint8(path, table)
+        key, u8 = resized_uint8(path, table, device=resize_device)
         latent = encoder.encode_uint8(u8, **encode_options)[0]
         sample = {"__key__": f"{first_key + idx:07d}", "ratio": key, "latent": latent.to(torch.bfloat16).cpu(), "emb": emb}
         if pooled is not None:
@@ -122,6 +127,8 @@ def main(argv=None) -> None:
     ap.add_argument("--seed", type=int, default=0, help="AutoencoderKL: seed of the sampling noise's generator")
     ap.add_argument("--mode", action="store_true", help="AutoencoderKL: store the distribution's mode, not a sample")
     ap.add_argument("--no-shift", action="store_true", help="AutoencoderKL: do not subtract the config's shift_factor")
+    ap.add_argument("--device-resize", action="store_true",
+                    help="resize on the device with the Pillow-exact HIP kernel instead of with Pillow (the same shard bytes)")
     ap.add_argument("images", nargs="+")
     a = ap.parse_args(argv)
     from .autoencoder_kl import load_vae_encoder, vae_class
@@ -129,7 +136,7 @@ def main(argv=None) -> None:
     enc = load_vae_encoder(a.vae, device=a.device)
     table = table_for_resolution(a.resolution)
     opts = encode_options(vae_class(read_config(a.vae)), a.seed, a.mode, a.no_shift, a.device)
-    samples = list(extract_samples(enc, a.images, table, a.first_key, **opts))
+    samples = list(extract_samples(enc, a.images, table, a.first_key, resize_device=a.device if a.device_resize else None, **opts))
     write_shard(a.out, samples)
     print(f"{a.out}: {len(samples)} sample(s)")
 

@@ -116,6 +116,9 @@ SIGNATURES = {
     "yat_dcae_conv3x3_down": (I, [I, I, I, I, I, P, P, P, I, P, P]),
     "yat_dcae_conv3x3_mean": (I, [I, I, I, I, I, P, P, P, I, P, P]),
     "yat_dcae_image_from_uint8": (I, [I64, P, P, P, P]),
+    "yat_image_resize_plan": (I, [I, I, I, I]),
+    "yat_image_resize_workspace_bytes": (U64, [I, I, I, I]),
+    "yat_image_resize_u8": (I, [I, I, I, I, I, I, P, P, P, P, P]),
     "yat_vae_groupnorm_workspace_bytes": (U64, [I, I, I, I]),
     "yat_vae_groupnorm": (I, [I, I, I, I, F, P, P, P, I, P, P, P]),
     "yat_vae_attn_fwd": (I, [I, I, I, P, P, P, I, P, I, P]),

@@ -879,6 +879,28 @@ def dcae_image_from_uint8(x, out=None):
     return out
 
 
+# --------------------------------------------------------------------------------- image ingest (yat_amd/image.py)
+def image_resize_u8(src, tables, ksize_h, ksize_v, dst):
+    """[H, W, 3] uint8 -> [th, tw, 3] uint8, Pillow's antialiased bilinear resize (yat_image_resize_u8).  ``tables``: the packed
+    int32 block of yat_amd.image.packed_tables on the device (None when neither size changes); ``dst`` may be a slot of a
+    batch.  The workspace of the two-launch plan is allocated here, per call."""
+    if src.dtype != torch.uint8 or src.dim() != 3 or src.shape[-1] != 3 or not src.is_contiguous():
+        raise ValueError("image_resize_u8 wants a contiguous [H, W, 3] uint8 source")
+    if dst.dtype != torch.uint8 or dst.dim() != 3 or dst.shape[-1] != 3 or not dst.is_contiguous():
+        raise ValueError("image_resize_u8 wants a contiguous [th, tw, 3] uint8 destination")
+    if tables is not None and (tables.dtype != torch.int32 or not tables.is_contiguous()):
+        raise TypeError("image_resize_u8: tables must be a contiguous int32 tensor")
+    (H, W, _), (th, tw, _) = src.shape, dst.shape
+    want = ((2 + int(ksize_h)) * tw if ksize_h else 0) + ((2 + int(ksize_v)) * th if ksize_v else 0)
+    if (tables.numel() if tables is not None else 0) != want:
+        raise ValueError(f"image_resize_u8: tables hold {0 if tables is None else tables.numel()} entries, these sizes need {want}")
+    nbytes = _l.load().yat_image_resize_workspace_bytes(H, W, th, tw)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device) if nbytes else None
+    rc = _lib().yat_image_resize_u8(H, W, th, tw, int(ksize_h), int(ksize_v), _p(src), _p(tables), _p(dst), _p(ws), _stream())
+    _l.check(rc, "yat_image_resize_u8")
+    return dst
+
+
 # --------------------------------------------------------------------------------- AutoencoderKL decoder (yat_amd/autoencoder_kl.py)
 def vae_groupnorm_workspace_bytes(B, HW, C, G):
     return int(_lib().yat_vae_groupnorm_workspace_bytes(B, HW, C, G))
