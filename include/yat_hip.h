@@ -83,7 +83,11 @@ uint64_t yat_gemm_epilogue_size(void);   /* sizeof(yat_gemm_epilogue) in this bu
 /* C[M,N] = epilogue(A_op * B_op).  a_t=0: A is [M,K] (k contiguous); a_t=1: A is [K,M].
  * b_t=0: B is [N,K] (k contiguous, nn.Linear weight layout); b_t=1: B is [K,N].
  * (0,0) forward y = x W^T; (0,1) dgrad dx = dy W; (1,1) wgrad dW = dy^T x; (1,0) x^T W^T.
- * Epilogue order: +bias -> round bf16 -> aux_out -> activation -> *gate (rounded) -> +residual.  */
+ * Epilogue order: +bias -> round bf16 -> aux_out -> activation -> *gate (rounded) -> +residual.
+ * Leading dimensions (elements): lda, ldb multiples of 8, ldc and the epilogue's multiples of 4, and each covers its row --
+ * lda >= K (a_t=0) or M (a_t=1), ldb >= K (b_t=0) or N (b_t=1), ldc >= N, a nonzero ld_residual / ld_aux >= N (0 = ldc),
+ * ld_pre_add / ld_dact_z >= N, ld_glu_u >= 2N (and then ldc >= 2N); ld_gate = 0 is one gate row for every batch.  Rows that
+ * would overlap are refused with YAT_EINVAL before any launch.  */
 int yat_gemm_bf16(int a_t, int b_t, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
                   void* C, int ldc, const yat_gemm_epilogue* ep, yat_stream_t stream);
 

@@ -16,6 +16,7 @@ Integer outputs (mask, kv_len) and the optimizer are checked bit-exactly.
 All checks of a test are evaluated and printed before the test fails.
 The row and strip kernels (csrc/rowops.hip, yat_transpose_bf16): dispatch classes and ragged edges in test_rowops_gpu.py.
 Linear attention (csrc/linear_attn.hip): token classes, grid totals, strides, dead rows and hidden state in test_linear_attn_gpu.py.
+The GEMM family (csrc/gemm.hip, csrc/gemm256.hip): leading dimensions, views, the 8-byte epilogue and refused arguments in test_gemm_layout_gpu.py.
 """
 import math
 

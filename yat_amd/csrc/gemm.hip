@@ -213,6 +213,7 @@ static int fill_gemm_p(int a_t, int b_t, int M, int N, int K, const void* A, int
     if (a_t && (M & 7)) return YAT_EINVAL;             // 16-B chunks along m
     if (b_t && (N & 7)) return YAT_EINVAL;
     if (!b_t && (K & 7)) return YAT_EINVAL;
+    if (lda < (a_t ? M : K) || ldb < (b_t ? N : K) || ldc < N) return YAT_EINVAL;   // a leading dimension covers its row
     p = GemmP{};
     p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = (bf16_t*)C;
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
@@ -228,6 +229,7 @@ static int fill_gemm_p(int a_t, int b_t, int M, int N, int K, const void* A, int
         p.ldaux = ep->ld_aux ? ep->ld_aux : ldc; p.gate_ld = ep->ld_gate; p.rows_per_batch = ep->rows_per_batch;
         p.act = ep->activation;
         if (p.act < 0 || p.act > 2) return YAT_EINVAL;
+        if ((ep->ld_residual && ep->ld_residual < N) || (ep->ld_aux && ep->ld_aux < N)) return YAT_EINVAL;   // (0: ldc)
         if (p.gate && (p.gate_ld & 3)) return YAT_EINVAL;
         p.pre_add = (const bf16_t*)ep->pre_add; p.ld_pre = ep->ld_pre_add;
         if (p.pre_add && ((p.ld_pre & 3) || p.ld_pre < N)) return YAT_EINVAL;
