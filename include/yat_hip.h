@@ -276,8 +276,13 @@ int yat_lokr_project(int out_l, int out_k, int in_m, int in_n, int r, const void
  *   adapter(x) = T1_flat P^T  (yat_gemm_bf16, K = in_m*r)       w2_b := identity)
  *   dx += (dy P)' w2_b,  d_P = dy^T T1_flat (then yat_lokr_project -> d_w1, d_w2_a),  d_w2_b = (dy P)'^T x'
  * -- the last one has r x in_n outputs and a rows-long reduction: out[q, n] (+)= bf16(scale * sum_row a[row, q] * x[row, n]),
- * q < r_out.  a: bf16 [rows, R] (R = 8 or 16), x: bf16 [rows, N] with row stride ldx (N % 8 == 0; column blocks of 128 are
- * separate workgroups, so N may be a whole layer width: the d_A / d_B of a plain LoRA adapter), out: bf16 [r_out, ldo]. */
+ * q < r_out.  a: bf16 [rows, R] (R = 8, 16, 32, 64 or 128), x: bf16 [rows, N] with row stride ldx (N % 8 == 0; column blocks of
+ * 128 are separate workgroups, so N may be a whole layer width: the d_A / d_B of a plain LoRA adapter), out: bf16 [r_out, ldo].
+ * Workspace (fp32 partials, summed in a fixed order by a second launch: no atomics, equal bits on every call):
+ *   G * R * ceil(N / 128) * 128 * 4 bytes, with nblk = ceil(N / 128) and
+ *   R <= 16:  G = min(ceil(rows / 256), max(32, 512 / nblk))
+ *   R >= 32:  G = min(ceil(rows / 128), max(4, 256 / nblk))   (at most 16 MiB while N <= 8192)
+ * R >= 32 splits the R x 128 accumulator block over the four waves (by q, at R = 32 by column half too) instead of the k-steps. */
 /* the two row-streaming products of that path: backward=0: io[rows, R] = a[rows, N] w2_b^T;
  * backward=1: io[rows, N] = bf16(bf16(a[rows, R] w2_b) + io)   (w2_b: bf16 [R, N], R = 8 or 16, N <= 128, N % 8 == 0) */
 int yat_lokr_rows(int64_t rows, int N, int R, int backward, const void* w2_b, const void* a, void* io, yat_stream_t stream);
@@ -291,13 +296,16 @@ int yat_lokr_rows_fwd_flat(int64_t rows, int N, int R, int in_m, const void* w2_
 int yat_dropout(int64_t n, float p, uint64_t seed, int backward_add, const void* x, void* io, yat_stream_t stream);
 /* plain LoRA with the adapter term as the base GEMM's second operand pair (yat_gemm_epilogue.a2 = T = x A^T in K2 = 64 columns with
  * x's row stride, b2 = scaling * lora_B with the weight's row stride): this entry writes b2 for EVERY adapter in one launch --
- * dst[tgt + n in + q] = bf16(scale * src[off + q out + n]), q < R (8 or 16), n < out, with table[4 e ..] = {off, tgt, out, in} as int64
+ * dst[tgt + n in + q] = bf16(scale * src[off + q out + n]), q < R (8, 16, 32, 64 or 128; R <= in), n < out, with table[4 e ..] = {off, tgt, out, in} as int64
  * (device memory), dst a zero-filled shadow of the model's flat weights; in % 8 == 0 and tgt % 8 == 0 (16-byte rows) */
 int yat_lora_scatter_b(int entries, int max_out, int R, float scale, const void* table, const void* src, void* dst,
                        yat_stream_t stream);
 /* rank-R expansion over a whole layer width (plain LoRA, peft lora/layer.py [RECALL]; the reference's LoraConfig branch at
  * common/trainer.py:214-219): io[row, n] = f(sum_q h[row, q] * w[q, n]), h: bf16 [rows, R], w: bf16 [R, N], io: bf16 [rows, ldio];
- * residual=0: io = bf16(bf16(sum) * scale)  (lora_B(lora_A(x)) * scaling);  residual=1: io = bf16(bf16(sum) + io)  (dx += dT A) */
+ * residual=0: io = bf16(bf16(sum) * scale)  (lora_B(lora_A(x)) * scaling);  residual=1: io = bf16(bf16(sum) + io)  (dx += dT A).
+ * R = 8 or 16: scalar FMAs from an fp32 LDS image of w (an HBM-bound stream);  R = 32, 64 or 128: v_mfma_f32_16x16x32_bf16 with
+ * w's fragments resident in registers (w 16-byte aligned), fp32 accumulation.  N % 8 == 0, ldio % 8 == 0, ldio >= N; nothing
+ * outside [rows, N] is written. */
 int yat_rank_expand(int64_t rows, int N, int R, const void* w, const void* h, void* io, int ldio, float scale, int residual,
                     yat_stream_t stream);
 uint64_t yat_lokr_small_wgrad_workspace_bytes(int64_t rows, int R, int N);

@@ -359,6 +359,195 @@ __global__ __launch_bounds__(256) void lokr_wide_rows_kernel(int64_t rows, int N
     }
 }
 
+// The same expansion for R = 32, 64, 128 on the matrix cores: at R = 64 the stream above needs 64 x 8 FMAs per 16 bytes stored
+// and is bound by vector issue.  A wave owns 64 columns and walks 16-row tiles; h is k-contiguous, so a lane's fragment of
+// v_mfma_f32_16x16x32_bf16 (8 consecutive q of one row) is one 16-byte global load; w is k-strided, so the workgroup stages its
+// 256-column block once as a row-major LDS image (zeros past N) and every wave fetches its R / 32 x 4 fragments with
+// ds_read_b64_tr_b16 and keeps them in registers over the whole row loop (at most 64 VGPRs).  With w as the first operand a lane
+// ends up with 4 consecutive columns of one row per tile; the four tiles of a wave interleave their columns (MFMA row i of tile j
+// is column 16 (i >> 2) + 4 j + (i & 3) -- the transposing read takes any 8-byte piece per lane, so the permutation is free), so
+// a lane holds 16 consecutive columns: two 16-byte stores, 128 contiguous bytes of a row from its four lanes.
+template <int R>
+__global__ __launch_bounds__(256) void lora_expand_mfma_kernel(int64_t rows, int N, int ldio, const bf16_t* wsrc, const bf16_t* h,
+                                                               bf16_t* io, float scale, int residual) {
+    constexpr int CB = 256, KS = R / 32;
+    __shared__ __attribute__((aligned(16))) char wimg[R * CB * 2];        // [R][CB] bf16, 512-byte rows
+    const int n0 = blockIdx.y * CB;
+    for (int v = threadIdx.x; v < R * (CB / 8); v += 256) {
+        const int q = v / (CB / 8), c = v - q * (CB / 8), n = n0 + c * 8;
+        u32x4 t = u32x4{0u, 0u, 0u, 0u};
+        if (n < N) t = *reinterpret_cast<const u32x4*>(wsrc + (int64_t)q * N + n);
+        *reinterpret_cast<u32x4*>(wimg + q * (CB * 2) + c * 16) = t;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane >> 4, li = lane & 15;
+    const int n = n0 + wave * 64 + g * 16;                    // this lane's 16 columns
+    if (n0 + wave * 64 >= N) return;                          // (after the only barrier)
+    bf16x8 wf[KS][4];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t qa = 32 * ks + 8 * g + (li >> 2), col = wave * 64 + 16 * (li & 3) + 4 * j;
+            wf[ks][j] = cat4(lds_read_tr4(wimg, qa * (CB * 2) + col * 2), lds_read_tr4(wimg, (qa + 4) * (CB * 2) + col * 2));
+        }
+    const bool lo = n < N, hi = n + 8 < N;
+    const int64_t tiles = (rows + 15) >> 4;
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const int64_t row = t * 16 + li;
+        const bool rv = row < rows;
+        bf16x8 hf[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) hf[ks][e] = (__bf16)0.0f;
+            if (rv) hf[ks] = *reinterpret_cast<const bf16x8*>(h + row * R + 32 * ks + 8 * g);
+        }
+        bf16_t* dp = io + row * ldio + n;
+        float d[16] = {};
+        if (residual) {
+            if (rv && lo) unpack8(*reinterpret_cast<const u32x4*>(dp), d);
+            if (rv && hi) unpack8(*reinterpret_cast<const u32x4*>(dp + 8), d + 8);
+        }
+        float o[16];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) acc = mfma16(wf[ks][j], hf[ks], acc);      // acc[r] = sum[row][n + 4 j + r]
+            o[4 * j] = acc[0]; o[4 * j + 1] = acc[1]; o[4 * j + 2] = acc[2]; o[4 * j + 3] = acc[3];
+        }
+        if (residual) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) o[e] = rbf(o[e]) + d[e];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) o[e] = rbf(o[e]) * scale;
+        }
+        if (rv && lo) *reinterpret_cast<u32x4*>(dp) = pack8(o);
+        if (rv && hi) *reinterpret_cast<u32x4*>(dp + 8) = pack8(o + 8);
+    }
+}
+
+// yat_lokr_small_wgrad for R = 32, 64, 128: the same stream through LDS (128-column blocks of x, 16-byte loads all in flight
+// before the first LDS store, both images read with ds_read_b64_tr_b16, fp32 partials per workgroup summed by
+// lokr_small_wgrad_final_kernel), but the R x 128 accumulator block no longer fits "every wave holds all of it and the waves split
+// the k-steps" (2 R accumulator registers per wave): here the four waves split the block itself -- by q, and at R = 32 by column
+// half as well -- and every wave runs all k-steps of a chunk, so no cross-wave sum is left and the partial is written from the
+// accumulators.  R = 32: 1 q-tile x 4 column tiles per wave; 64: 1 x 8; 128: 2 x 8 (64 accumulator registers).  Chunks of 128
+// rows: the a image is 256 R bytes (64-, 128- or 256-byte rows, 16-byte pieces XOR-swizzled like the x image within a row).
+template <int R>
+__global__ __launch_bounds__(256) void lora_wgrad_mfma_kernel(int64_t rows, int N, int ldx, int npad, const bf16_t* A,
+                                                              const bf16_t* X, float* partial) {
+    constexpr int CH = 128;                                  // rows per staged chunk = 4 k-steps of 32
+    constexpr int AV = R / 8;                                // 16-byte pieces per row of a
+    constexpr int WQ = R / 16 < 4 ? R / 16 : 4, WC = 4 / WQ; // waves along q and along the columns
+    constexpr int QT = R / 16 / WQ, CT = 8 / WC;             // tiles per wave
+    constexpr int NA = CH * AV / 256;                        // 16-byte loads of a per thread and chunk
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* ximg = smem;                                       // [CH][128] bf16, 256-byte rows, piece ^= sw_swz(row)
+    char* aimg = smem + CH * 256;                            // [CH][R] bf16, piece ^= sw_swz(row) & (AV - 1)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wq = wave % WQ, wc = wave / WQ;
+    const int n0 = blockIdx.y * 128;
+    const int Nb = N - n0 < 128 ? N - n0 : 128;
+    const int VPR = Nb >> 3, ntile = (Nb + 15) >> 4;
+    f32x4 acc[QT][CT];
+#pragma unroll
+    for (int a = 0; a < QT; ++a)
+#pragma unroll
+        for (int t = 0; t < CT; ++t) acc[a][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const uint32_t g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
+    const int64_t nchunk = (rows + CH - 1) / CH;
+    for (int64_t ck = blockIdx.x; ck < nchunk; ck += gridDim.x) {
+        const int64_t r0 = ck * CH;
+        const int nr = (int)(rows - r0 < CH ? rows - r0 : CH);
+        u32x4 xv[8], av[NA];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int v = threadIdx.x + 256 * i;
+            const int r = v / VPR, c = v - r * VPR;
+            xv[i] = u32x4{0u, 0u, 0u, 0u};                   // rows past the end contribute zeros (never stale LDS bits)
+            if (v < CH * VPR && r < nr) xv[i] = *reinterpret_cast<const u32x4*>(X + (r0 + r) * ldx + n0 + c * 8);
+        }
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const int v = threadIdx.x + 256 * i;
+            const int r = v / AV;
+            av[i] = u32x4{0u, 0u, 0u, 0u};
+            if (r < nr) av[i] = *reinterpret_cast<const u32x4*>(A + r0 * R + (int64_t)v * 8);
+        }
+        __syncthreads();                                     // previous chunk fully consumed
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int v = threadIdx.x + 256 * i;
+            const int r = v / VPR, c = v - r * VPR;
+            if (v < CH * VPR) *reinterpret_cast<u32x4*>(ximg + r * 256 + ((c ^ sw_swz(r)) << 4)) = xv[i];
+        }
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const int v = threadIdx.x + 256 * i;
+            const int r = v / AV, c = v - r * AV;
+            *reinterpret_cast<u32x4*>(aimg + r * (R * 2) + ((c ^ (sw_swz(r) & (AV - 1))) << 4)) = av[i];
+        }
+        __syncthreads();
+        // (not unrolled: with the four k-steps flattened the compiler hoists every LDS read of the chunk and parks the fragments
+        // in AGPRs -- 234 VGPRs + 160 AGPRs at R = 64, measured 195 us against 71 us rolled at N = 2240, 32768 rows)
+#pragma unroll 1
+        for (int kk = 0; kk < CH / 32; ++kk) {
+            const uint32_t ra = kk * 32 + 8 * g + q, rb = ra + 4;
+            bf16x8 af[QT];
+#pragma unroll
+            for (int a = 0; a < QT; ++a) {
+                const uint32_t pc = 2 * (wq * QT + a) + (p >> 1);                       // piece of columns 16 tile + 4 p ..
+                af[a] = cat4(lds_read_tr4(aimg, ra * (R * 2) + ((pc ^ (sw_swz(ra) & (AV - 1))) << 4) + (p & 1) * 8),
+                             lds_read_tr4(aimg, rb * (R * 2) + ((pc ^ (sw_swz(rb) & (AV - 1))) << 4) + (p & 1) * 8));
+            }
+#pragma unroll
+            for (int t = 0; t < CT; ++t) {
+                const int tt = wc * CT + t;
+                if (tt < ntile) {
+                    const uint32_t pc = 2 * tt + (p >> 1);
+                    const bf16x8 xf = cat4(lds_read_tr4(ximg, ra * 256 + ((pc ^ sw_swz(ra)) << 4) + (p & 1) * 8),
+                                           lds_read_tr4(ximg, rb * 256 + ((pc ^ sw_swz(rb)) << 4) + (p & 1) * 8));
+#pragma unroll
+                    for (int a = 0; a < QT; ++a) acc[a][t] = mfma16(af[a], xf, acc[a][t]);   // out[16 qtile + 4 g + r][16 tt + li]
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < QT; ++a)
+#pragma unroll
+        for (int t = 0; t < CT; ++t) {
+            const int nn = (wc * CT + t) * 16 + (lane & 15);
+            if (nn < Nb) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    partial[((int64_t)blockIdx.x * R + (wq * QT + a) * 16 + 4 * g + r) * npad + n0 + nn] = acc[a][t][r];
+            }
+        }
+}
+
+template <int R>
+int small_wgrad_mfma_launch(int G, int nblk, hipStream_t st, int64_t rows, int N, int ldx, int npad, const bf16_t* a,
+                            const bf16_t* x, float* ws) {
+    constexpr int lds = 128 * (256 + 2 * R);                 // x image 32 KiB + a image 8 / 16 / 32 KiB
+    static bool attr_set = false;
+    if (!attr_set) {
+        if (hipFuncSetAttribute((const void*)lora_wgrad_mfma_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
+            hipSuccess)
+            return YAT_EINVAL;
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((lora_wgrad_mfma_kernel<R>), dim3(G, nblk), dim3(256), lds, st, rows, N, ldx, npad, a, x, ws);
+    return YAT_OK;
+}
+
+// the padded ranks of plain LoRA (yat_rank_expand, yat_lokr_small_wgrad, yat_lora_scatter_b)
+bool rank_ok(int R) { return R == 8 || R == 16 || R == 32 || R == 64 || R == 128; }
+
 int fill(LokrP& p, int out_l, int out_k, int in_m, int in_n, int r, const void* w1, const void* w2a, const void* w2b,
          float scale, int ld) {
     if (out_l <= 0 || out_k <= 0 || in_m <= 0 || in_n <= 0 || r <= 0 || r > 64 || !w1 || !w2a || !w2b ||
@@ -533,19 +722,31 @@ static int lokr_rows_launch(int64_t rows, int N, int R, int backward, const void
 
 int yat_lora_scatter_b(int entries, int max_out, int R, float scale, const void* table, const void* src, void* dst,
                        yat_stream_t stream) {
-    if (entries <= 0 || entries > 65535 || max_out <= 0 || (R != 8 && R != 16) || !table || !src || !dst) return YAT_EINVAL;
+    if (entries <= 0 || entries > 65535 || max_out <= 0 || !rank_ok(R) || !table || !src || !dst) return YAT_EINVAL;
     const dim3 grid((max_out + 255) / 256, entries), block(256);
-    if (R == 8) hipLaunchKernelGGL((lora_scatter_b_kernel<8>), grid, block, 0, (hipStream_t)stream, (const int64_t*)table, scale,
-                                   (const bf16_t*)src, (bf16_t*)dst);
-    else hipLaunchKernelGGL((lora_scatter_b_kernel<16>), grid, block, 0, (hipStream_t)stream, (const int64_t*)table, scale,
-                            (const bf16_t*)src, (bf16_t*)dst);
+#define YAT_SCATTER(RR) hipLaunchKernelGGL((lora_scatter_b_kernel<RR>), grid, block, 0, (hipStream_t)stream, (const int64_t*)table, \
+                                           scale, (const bf16_t*)src, (bf16_t*)dst)
+    if (R == 8) YAT_SCATTER(8); else if (R == 16) YAT_SCATTER(16); else if (R == 32) YAT_SCATTER(32);
+    else if (R == 64) YAT_SCATTER(64); else YAT_SCATTER(128);
+#undef YAT_SCATTER
     YAT_CHECK_LAUNCH();
     return YAT_OK;
 }
 
 int yat_rank_expand(int64_t rows, int N, int R, const void* w, const void* h, void* io, int ldio, float scale, int residual,
                     yat_stream_t stream) {
-    if (rows <= 0 || (R != 8 && R != 16) || N <= 0 || (N & 7) || (ldio & 7) || ldio < N || !w || !h || !io) return YAT_EINVAL;
+    if (rows <= 0 || !rank_ok(R) || N <= 0 || (N & 7) || (ldio & 7) || ldio < N || !w || !h || !io) return YAT_EINVAL;
+    if (R > 16) {                                            // matrix cores: 256-column blocks, 16-row tiles
+        const int nblk = (N + 255) / 256;
+        const int64_t tiles = (rows + 15) / 16;
+        const dim3 grid((unsigned)(tiles > 2048 / nblk + 1 ? 2048 / nblk + 1 : tiles), nblk);
+#define YAT_EXPAND(RR) hipLaunchKernelGGL((lora_expand_mfma_kernel<RR>), grid, dim3(256), 0, (hipStream_t)stream, rows, N, ldio, \
+                                          (const bf16_t*)w, (const bf16_t*)h, (bf16_t*)io, scale, residual)
+        if (R == 32) YAT_EXPAND(32); else if (R == 64) YAT_EXPAND(64); else YAT_EXPAND(128);
+#undef YAT_EXPAND
+        YAT_CHECK_LAUNCH();
+        return YAT_OK;
+    }
     const int nblk = (N + 511) / 512;
     int64_t g64 = (rows + 3) / 4;
     const int gx = (int)(g64 > 2048 / nblk + 1 ? 2048 / nblk + 1 : g64);
@@ -559,7 +760,13 @@ int yat_rank_expand(int64_t rows, int N, int R, const void* w, const void* h, vo
     return YAT_OK;
 }
 
-static int small_wgrad_groups(int64_t rows, int nblk) {
+static int small_wgrad_groups(int64_t rows, int R, int nblk) {
+    if (R > 16) {                                            // 128-row chunks, ~one workgroup per CU over all column blocks: the
+        const int64_t nchunk = (rows + 127) / 128;           // partials are G x R x npad fp32 (32 groups would be 180 MB at
+        int64_t g = 256 / nblk;                              // R = 128, N = 11200); at most 16 MiB while N <= 8192, four
+        if (g < 4) g = 4;                                    // groups beyond
+        return (int)(nchunk < g ? nchunk : g);
+    }
     const int64_t nchunk = (rows + 255) / 256;
     int64_t g = 512 / nblk;                                  // ~two workgroups per CU over all column blocks
     if (g < 32) g = 32;
@@ -568,16 +775,32 @@ static int small_wgrad_groups(int64_t rows, int nblk) {
 
 uint64_t yat_lokr_small_wgrad_workspace_bytes(int64_t rows, int R, int N) {
     const int nblk = (N + 127) / 128;
-    return (uint64_t)small_wgrad_groups(rows, nblk) * R * nblk * 128 * sizeof(float);
+    return (uint64_t)small_wgrad_groups(rows, R, nblk) * R * nblk * 128 * sizeof(float);
 }
 
 int yat_lokr_small_wgrad(int64_t rows, int R, int N, int r_out, const void* a, const void* x, int ldx, void* out, int ldo,
                          float scale, int accumulate, void* workspace, yat_stream_t stream) {
-    if (rows <= 0 || (R != 8 && R != 16) || N <= 0 || (N & 7) || (ldx & 7) || ldx < N || ldo < N || r_out <= 0 || r_out > R ||
+    if (rows <= 0 || !rank_ok(R) || N <= 0 || (N & 7) || (ldx & 7) || ldx < N || ldo < N || r_out <= 0 || r_out > R ||
         !a || !x || !out || !workspace)
         return YAT_EINVAL;
     const int nblk = (N + 127) / 128, npad = nblk * 128;
-    const int G = small_wgrad_groups(rows, nblk);
+    const int G = small_wgrad_groups(rows, R, nblk);
+    const int n_out = r_out * N;
+    if (R > 16) {
+        hipStream_t st = (hipStream_t)stream;
+        const bf16_t* ap = (const bf16_t*)a;
+        const bf16_t* xp = (const bf16_t*)x;
+        float* ws = (float*)workspace;
+        const int rc = R == 32 ? small_wgrad_mfma_launch<32>(G, nblk, st, rows, N, ldx, npad, ap, xp, ws)
+                     : R == 64 ? small_wgrad_mfma_launch<64>(G, nblk, st, rows, N, ldx, npad, ap, xp, ws)
+                               : small_wgrad_mfma_launch<128>(G, nblk, st, rows, N, ldx, npad, ap, xp, ws);
+        if (rc != YAT_OK) return rc;
+        YAT_CHECK_LAUNCH();
+        hipLaunchKernelGGL(lokr_small_wgrad_final_kernel, dim3((n_out + 15) / 16), dim3(256), 0, st, G, R, N, npad, r_out, scale,
+                           (const float*)workspace, (bf16_t*)out, ldo, accumulate);
+        YAT_CHECK_LAUNCH();
+        return YAT_OK;
+    }
     const int lds = 256 * (128 + 16) * 2;                    // x image 64 KiB + a image 8 KiB
     static bool attr_set = false;
     if (!attr_set) {
@@ -589,7 +812,6 @@ int yat_lokr_small_wgrad(int64_t rows, int R, int N, int r_out, const void* a, c
     hipLaunchKernelGGL(lokr_small_wgrad_kernel, dim3(G, nblk), dim3(256), lds, (hipStream_t)stream, rows, R, N, ldx, npad,
                        (const bf16_t*)a, (const bf16_t*)x, (float*)workspace);
     YAT_CHECK_LAUNCH();
-    const int n_out = r_out * N;
     hipLaunchKernelGGL(lokr_small_wgrad_final_kernel, dim3((n_out + 15) / 16), dim3(256), 0, (hipStream_t)stream, G, R, N, npad,
                        r_out, scale, (const float*)workspace, (bf16_t*)out, ldo, accumulate);
     YAT_CHECK_LAUNCH();

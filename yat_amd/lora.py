@@ -8,11 +8,12 @@ Linear / 1x1 Conv with weight W [out, in]:
 with lora_A [r, in] kaiming-uniform(a=sqrt(5)), lora_B [out, r] zeros, every op in the module dtype (bf16).
 
 MI355X mapping (an ``AdapterSet`` of yat_amd/adapters.py, so the models' hooks do not change): the adapter set owns one flat
-bf16 buffer (per target: A [R, in] then B^T [R, out], R = the rank padded to 8 so every skinny GEMM keeps 16-byte rows; the
-padding rows stay exactly zero: their gradients are zero) with a flat gradient twin -- clip + AdamW and the data-parallel
+bf16 buffer (per target: A [R, in] then B^T [R, out], R = the rank padded to 8, 16, 32, 64 or 128 -- ranks above 128 raise --
+so every skinny GEMM keeps 16-byte rows and the rank-R kernels one instantiation per R; the padding rows stay exactly zero:
+their gradients are zero) with a flat gradient twin -- clip + AdamW and the data-parallel
 all-reduce are the usual single launches.  Per target and step:
     forward   T = x A^T (GEMM, N = R);  adapter = bf16(bf16(T B^T) * scaling)  (yat_rank_expand: a K = R product is all epilogue,
-              so it is a stream, not a GEMM) -> pre_add
+              so it is a stream, not a GEMM; from R = 32 the sum runs on the matrix cores) -> pre_add
     dgrad     dT = scaling * (dy B)     (GEMM, N = R, the scalar as a constant gate row);  dx += dT A   (yat_rank_expand)
     wgrad     d_B^T = scaling * T^T dy,  d_A = dT^T x  -- R x width outputs over a B*N-row reduction: yat_lokr_small_wgrad
 The dense weight gradients of the frozen base are never computed.  ``scaling`` is applied to the small side of each product
@@ -44,17 +45,18 @@ class LoRAAdapters(AdapterSet):
         self.dropout, self._seed, self._step = float(dropout or 0.0), int(seed), 0
         # [RECALL peft] scaling = lora_alpha / r, or lora_alpha / sqrt(r) with use_rslora
         self.scale = float(alpha) / (math.sqrt(int(r)) if use_rslora else int(r))
-        self.R = R = (self.r + 7) // 8 * 8
-        if R > 16:
-            raise NotImplementedError("LoRA rank > 16")
+        if self.r > 128:
+            raise NotImplementedError("LoRA rank > 128 (the rank-R kernels take a padded rank of at most 128)")
+        self.R = R = next(p for p in (8, 16, 32, 64, 128) if self.r <= p)
+        self.slot = slot = max(64, R)              # slab columns per adapter in forward_pair(): k2 stays a multiple of 64
         self._scan(model, targets)
         dev = model.flat_param.device
         self._gate = torch.full((max(max(e["out"] for e in self.entries), R),), self.scale, dtype=BF16, device=dev)
         # forward through the base GEMM's second operand pair (forward_pair()): scaling * lora_B of every adapter in the first R
         # columns of its target's rows of a zero-filled shadow of the flat weights, rebuilt by one launch per step; T in slab columns
-        # (per target: 64 columns must fit a row, and the rows of the shadow must be 16-byte aligned)
+        # (per target: a slot of max(64, R) columns must fit a row, and the rows of the shadow must be 16-byte aligned)
         for e in self.entries:
-            e["pair_ok"] = bool(pair) and e["inn"] >= 64 and e["w_off"] % 8 == 0
+            e["pair_ok"] = bool(pair) and e["inn"] >= slot and e["w_off"] % 8 == 0
         paired = [e for e in self.entries if e["pair_ok"]]
         self.pair = bool(paired)
         if self.pair:
@@ -118,32 +120,32 @@ class LoRAAdapters(AdapterSet):
 
     def forward_pair(self, x, w):
         """The adapter term of target view ``w`` as the second operand pair of the base GEMM (for ``adapted_linear``):
-        a2 = T = dropout(x) A^T in the first R of 64 slab columns per adapter (row stride of x), b2 = scaling * lora_B in the
-        shadow of the weights, k2 = 64.  base + adapter is accumulated in fp32 and rounded once (peft rounds u, u * scaling and
+        a2 = T = dropout(x) A^T in the first R of slot = max(64, R) slab columns per adapter (row stride of x), b2 =
+        scaling * lora_B in the shadow of the weights, k2 = slot.  base + adapter is accumulated in fp32 and rounded once (peft rounds u, u * scaling and
         the sum; with scaling a power of two the products are the same numbers)."""
         ents = self.lookup(w, self.model.flat_param)
         if not ents:
             return None
-        M, K, R = x.shape[0], x.shape[1], self.R
+        M, K, R, slot = x.shape[0], x.shape[1], self.R, self.slot
         e0 = ents[0][0]
         if not self.pair or not x.is_contiguous() or w.stride(0) != K or w.shape[0] != sum(e["out"] for e, _ in ents) \
-                or any(not e["pair_ok"] or e["inn"] != K or e["out"] != e0["out"] for e, _ in ents) or len(ents) * 64 > K \
+                or any(not e["pair_ok"] or e["inn"] != K or e["out"] != e0["out"] for e, _ in ents) or len(ents) * slot > K \
                 or (len(ents) > 1 and e0["out"] % 320 and e0["out"] % 256):
             return None
-        a2 = self._slabs.take(M, K, len(ents) * 64)
+        a2 = self._slabs.take(M, K, len(ents) * slot)
         for j, (e, row0) in enumerate(ents):
             assert row0 == j * e0["out"]
             a, _ = self._views(e, self.flat_param)
             # T is computed contiguous and copied into its slab columns (round-5 advisor: "write it straight into the slab"):
             # the weight gradient d_B = scaling T^T dy reads T through yat_lokr_small_wgrad, whose first operand has no row
             # stride -- an [M, 8] copy (0.5 MB at B = 32) is cheaper than a second T product.  Slots are fixed per target
-            # (plain LoRA never returns "plain"), so the columns R..63 of a slot stay the zeros the slab was created with.
+            # (plain LoRA never returns "plain"), so the columns R..slot of a slot stay the zeros the slab was created with.
             t = torch.empty(M, R, dtype=BF16, device=x.device)
             ops.gemm(self._dropped(e, x), a, t, M=M, N=R, K=K)                                # T = dropout(x) A^T
-            a2[:, j * 64:j * 64 + R].copy_(t)
+            a2[:, j * slot:j * slot + R].copy_(t)
             e["t"] = (x.data_ptr(), t)
-        b2 = self._flatB[(w.data_ptr() - self.model.flat_param.data_ptr()) // 2:][:w.shape[0] * K].view(w.shape[0], K)[:, :64]
-        return a2, b2, 64, (e0["out"] if len(ents) > 1 else 0)
+        b2 = self._flatB[(w.data_ptr() - self.model.flat_param.data_ptr()) // 2:][:w.shape[0] * K].view(w.shape[0], K)[:, :slot]
+        return a2, b2, slot, (e0["out"] if len(ents) > 1 else 0)
 
     def dgrad_term(self, dy, w, dx):
         hs = {}
