@@ -284,7 +284,8 @@ int yat_lokr_project(int out_l, int out_k, int in_m, int in_n, int r, const void
  *   R >= 32:  G = min(ceil(rows / 128), max(4, 256 / nblk))   (at most 16 MiB while N <= 8192)
  * R >= 32 splits the R x 128 accumulator block over the four waves (by q, at R = 32 by column half too) instead of the k-steps. */
 /* the two row-streaming products of that path: backward=0: io[rows, R] = a[rows, N] w2_b^T;
- * backward=1: io[rows, N] = bf16(bf16(a[rows, R] w2_b) + io)   (w2_b: bf16 [R, N], R = 8 or 16, N <= 128, N % 8 == 0) */
+ * backward=1: io[rows, N] = bf16(bf16(a[rows, R] w2_b) + io)   (w2_b: bf16 [R, N], R = 8 or 16, N <= 128, N % 8 == 0;
+ * rows * N / 8 <= 2^32 - 2^21: the 32-bit chunk index plus one grid stride must not wrap, YAT_EINVAL beyond) */
 int yat_lokr_rows(int64_t rows, int N, int R, int backward, const void* w2_b, const void* a, void* io, yat_stream_t stream);
 /* the forward one with T1 laid out as the second operand of the base Linear's GEMM (yat_gemm_epilogue.a2): t1_flat[m, j R + q] =
  * t1[m in_m + j, q], row stride ldt (= the row stride of x as the GEMM's A: [M, in]), rows = M in_m */

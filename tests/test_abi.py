@@ -71,6 +71,20 @@ def test_bad_arguments_are_rejected_without_a_gpu(built_lib):
     assert lib.yat_ln_modulate_fwd(4, 7, 4, 1e-6, 1, 1, 1, 8, 1, 1, 1, None) == -1     # D % 8 != 0
 
 
+def test_lokr_rows_bwd_rejects_chunk_counts_whose_index_would_wrap(built_lib):
+    """yat_lokr_rows, backward: the kernel walks rows * N / 8 chunks with a 32-bit index that advances by 8192 * 256 = 2^21 per
+    pass, so the last live index plus one stride has to stay below 2^32: every chunk count above 2^32 - 2^21 is YAT_EINVAL
+    before any launch (fake pointers, no device) -- also the counts just under 2^32 that the plain 32-bit range check let through."""
+    lib = ylib.load()
+    P, EINVAL = 0x7f0000001000, -1
+    for N in (128, 8):
+        cpr = N // 8
+        for chunks in ((1 << 32) - cpr, (1 << 32) - (1 << 20), (1 << 32) - (1 << 21) + cpr, 1 << 32, (1 << 32) + cpr):
+            assert chunks % cpr == 0
+            for R in (8, 16):
+                assert lib.yat_lokr_rows(chunks // cpr, N, R, 1, P, P, P, None) == EINVAL, (N, R, chunks)
+
+
 def test_linear_attn_bad_arguments_are_rejected_without_a_gpu(built_lib):
     """yat_linear_attn_fwd / _bwd: la_check and the stride / null checks return YAT_EINVAL before the first launch (csrc/
     linear_attn.hip), so the fake non-null pointers are never dereferenced and no GPU is needed."""

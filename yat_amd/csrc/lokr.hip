@@ -711,9 +711,11 @@ static int lokr_rows_launch(int64_t rows, int N, int R, int backward, const void
         return YAT_OK;
     }
     const int64_t chunks = rows * (N >> 3);
-    if (chunks > 0xffffffffll) return YAT_EINVAL;
     const int64_t g64 = (chunks + 255) / 256;
     const dim3 grid((unsigned)(g64 > 8192 ? 8192 : g64));
+    // the kernel's chunk index is 32 bits wide and advances by grid * 256: the last live index plus one stride has to stay below
+    // 2^32, or the index wraps back under `chunks` and the loop never ends (chunks <= 2^32 - 2^21 at the capped grid)
+    if (chunks - 1 + (int64_t)grid.x * 256 > 0xffffffffll) return YAT_EINVAL;
     if (R == 8) hipLaunchKernelGGL((lokr_rows_bwd_kernel<8>), grid, block, 0, st, (uint32_t)chunks, N, wb, ap, iop);
     else hipLaunchKernelGGL((lokr_rows_bwd_kernel<16>), grid, block, 0, st, (uint32_t)chunks, N, wb, ap, iop);
     YAT_CHECK_LAUNCH();
