@@ -113,7 +113,7 @@ def check_dwconv_stream_asm(asm_path: str) -> None:
 
 
 def check_gemm256_deep_asm(asm_path: str) -> None:
-    """csrc/gemm256.hip, DEEP schedule: the K loop's FAST form waits for an LDS-DMA batch with ``s_waitcnt vmcnt(n)``, n = the
+    """csrc/gemm256.hip: the K loop's FAST form waits for an LDS-DMA batch with ``s_waitcnt vmcnt(n)``, n = the
     pieces of the two younger batches -- correct only while a wave's loop iteration issues EXACTLY the pieces the source
     counts (PER_TILE = NAO + 2 NAH + 2 NB per K-tile) and no other vector-memory operation: one spilled register, one
     compiler-split load or a stray global access inside the loop and every gradient GEMM reads LDS bytes that have not

@@ -8,37 +8,53 @@
 //
 //   8 waves = 2 groups (g = wave>>2, rows [128g,128g+128)) x 4 column slices.  Waves w and w+4 land
 //   on the same SIMD.  Every K-tile is split into two 32-deep sub-steps, each a LOAD segment (12+
-//   ds_reads of the fragments, LDS-DMA issue for the next tile) followed by a COMPUTE segment (32..40
-//   MFMA 16x16x32 on registers only), separated by raw s_barriers.  Group 1 executes one extra
-//   barrier before its loop (group 0 one after), so on each SIMD one wave computes while the other
-//   loads: the matrix pipe sees back-to-back MFMA segments.
+//   ds_reads of the fragments and nothing else) followed by a COMPUTE segment (32..40 MFMA 16x16x32 on
+//   registers only, with the wave's LDS-DMA pieces issued between them), separated by raw s_barriers.
+//   Group 1 executes one extra barrier before its loop (group 0 one after), so on each SIMD one wave
+//   computes while the other loads: the matrix pipe sees back-to-back MFMA segments.
 //
-// LDS-DMA protocol (the only ordering for a DMA'd tile is the issuing wave's vmcnt + a barrier the
-// reader has passed).  Barrier bookkeeping: the n-th barrier of every wave is one rendezvous; group 0's
-// iteration t spans rendezvous 4t+1..4t+4, group 1's 4t+2..4t+5; tile u (stage u&1) is first read after
-// rendezvous 4u and last read before 4u+4.  DMA pieces are issued INSIDE compute segments, between
-// groups of four MFMAs (measured: with the issue in a load segment that segment outlasts the partner's
-// compute segment and the matrix pipe idles ~30 %): group 0 issues tile t+1 in COMPUTE(t,ks0) and waits
-// before its 4th barrier of iteration t; group 1 issues tile t+2 in COMPUTE(t,ks1) and waits for tile
-// t+1 before its 3rd barrier of iteration t -- both waits precede rendezvous 4t+4.
+// LDS-DMA protocol.  The only ordering for a DMA'd piece is the issuing wave's vmcnt + a barrier the reader has passed.  The
+// n-th barrier of every wave is one rendezvous.
+//   Numbering.  u = 2 t + kk numbers the 32-deep sub-steps (K-tile t, half kk).  Tile t lives in stage t & 1; the k-rows
+//           0..31 / 32..63 of an image are contiguous, so the halves form a four-slot ring in the two stages and half u + 4
+//           takes the place of half u.  Group 0's LOAD(u) ends with rendezvous 2u+1, its COMPUTE(u) with 2u+2; group 1's with
+//           2u+2 / 2u+3.  Hence half u is last read before rendezvous 2u+2, and half v is first read after rendezvous 2v.
+//   Issue.  Every wave fetches a share of every half, as one BATCH of pieces per COMPUTE segment (one piece every GAP MFMAs;
+//           with the issue in a LOAD segment that segment outlasts the partner's COMPUTE segment and the matrix pipe idles):
+//           group 0 issues its share of half u+3 in COMPUTE(u)  -- after 2u+1 > 2(u-1)+2: the slot's half u-1 has been read;
+//           group 1 issues its share of half u+4 in COMPUTE(u)  -- after 2u+2: half u has been read.
+//   Waits.  Counted: group 0 waits for its share of half u+3 at the end of COMPUTE(u+2) (before 2u+6, the first read of it)
+//           with its two younger batches still in flight, s_waitcnt vmcnt(n(u+1) + n(u+2)) = the pieces of one K-tile; group 1
+//           waits for its share of half u+4 at the end of LOAD(u+3) (before 2u+8), again past two younger batches.  The counts
+//           hold only while a loop iteration issues exactly the pieces the source counts and no other vector-memory
+//           operation: yat_amd/build.py (check_gemm256_deep_asm) checks that on the compiler's assembly at every build.  The
+//           prologue fetches tile 0 in full and then issues the batches a running loop would have issued before iteration 0,
+//           so the same counts hold from the first iteration; the last iterations (a batch of the window is missing or
+//           belongs to the ragged last K-tile, whose pieces take the per-lane CHECKED form) wait with vmcnt(0).
+//   k-contiguous A (forward and input-gradient layouts).  A 128-B row of this image carries both halves of a row of A, so
+//           it cannot be refilled per half -- but rows [128g, 128g+128) are read by group g alone: group g issues its own 128
+//           rows of tile t+2 in COMPUTE(t, kk = 1), first in the batch, right after its own last read of tile t, and waits for
+//           them before the rendezvous that precedes its LOAD(t+2, kk = 0).  A k-strided A (weight gradient, `tn`) is
+//           fetched per half like B.
+//   k-contiguous B (forward layouts).  Both groups read every column of B, so there is no such private part; its LDS image is
+//           HALF-MAJOR instead ([half][column][4 chunks of 16 B], see B_KH in the kernel body): piece for piece the shape of
+//           the k-strided image, fetched per half by the same batches under the same counts.
+// A piece has 4..6 segments (1.0..1.5 K-tiles) to land.
 //
-// DEEP schedule (round 4: layouts with a k-strided B operand, the input- and weight-gradient GEMMs; round 5: every layout -- a
-// k-contiguous B operand gets a half-major LDS image of the same piece shape, see B_KH below).  The two-stage ring above
-// gives a piece 2..4 of the 4 segments of a K-tile to land: enough for the Infinity Cache, short for HBM under load (operands
-// from HBM cost the same launches +10..+25 % at the sustained clock, scripts/gemm_sustained_probe.py).  The LDS images are
-// unchanged, but a k-strided image is refilled per 32-deep HALF (k-rows 0..31 / 32..63 are contiguous: a four-slot ring of
-// halves in the same two stages) as soon as group 1 has read it, and the rows of a k-contiguous A image -- private to one
-// wave group -- are refilled by that group right after its own last read:
-//   u = 2 t + kk numbers the 32-deep sub-steps; group 0's LOAD(u) ends with rendezvous 2u+1, its COMPUTE(u) with 2u+2;
-//   group 1's with 2u+2 / 2u+3.  Half u is last read before rendezvous 2u+2 and half v first read after rendezvous 2v.
-//   group 0 issues its share of half u+3 in COMPUTE(u) (after 2u+1 > 2(u-1)+2) and waits for it at the end of COMPUTE(u+2)
-//           (before 2u+6) with two younger batches still in flight:  s_waitcnt vmcnt(n(u+1) + n(u+2));
-//   group 1 issues its share of half u+4 in COMPUTE(u) (after 2u+2) and waits at the end of LOAD(u+3) (before 2u+8), again
-//           past two younger batches;
-//   k-contiguous A (input gradient): group g issues its own 128 rows of tile t+2 in COMPUTE(t, ks1), first in the batch, and
-//           waits before the rendezvous that precedes its LOAD(t+2, ks0).
-// A piece now has 4..6 segments (1.0..1.5 K-tiles) to land instead of 2..4.  Same pieces, same LDS bytes, same fragment
-// reads, same MFMA order: results are bit-identical to the two-stage schedule (-DYAT_GEMM_DEEP=0).
+// Predecessor.  Until round 4 (k-strided B) / round 5 (every layout) the K loop was a two-stage ring of whole tiles: group 0
+// issued tile t+1 in COMPUTE(t, 0), group 1 tile t+2 in COMPUTE(t, 1) (forward layouts: every wave tile t+1 in LOAD(t, 0)), all
+// waits vmcnt(0) before rendezvous 4t+4.  A piece then had 2..4 segments to land: enough for the Infinity Cache, short for HBM
+// under load -- operands from HBM cost the same launches +10..+25 % at the sustained clock (scripts/gemm_sustained_probe.py).
+// This schedule fills the same LDS bytes with the same pieces and keeps the fragment reads and the MFMA order, so it was
+// bit-identical to the two-stage build over 113 cases (profiles/r04_c_gemm_hash_deep_equals_two_stage.txt,
+// profiles/r05_a_gemm_hash_kh_deep_equals_r04.txt) and took the cold / hot gap from 15..24 % to 2..6 % and the step from 79.6
+// to 77.4 ms (profiles/r04_a_*, r04_b_gemm_deep_in_step_ab.txt; forward layouts: r05_a_gemm_kh_deep_step_ab.txt).  What its
+// switches had decided for the forward layouts before that: all DMA in compute segments + 4..6 % on the shapes alone but 2.4 ms
+// slower in the step; the pieces behind the fragment reads of LOAD(t, 0) + 3..4 % alone, 84.4 -> 84.6 ms in the step.  The
+// two-stage loop, its build switches (DMA placement, early rendezvous, ablations) and its s_memtime stamps
+// (profiles/r02_h_gemm_ablation.txt, r02_k_gemm_stamps.txt, r02_n_gemm_stamps.txt, r02_t_gemm_energy_ablation.txt) can last be
+// read at commit 4a098f80e878c3dca5c41c4d5967b747e19b3a55; that this file compiles to the same instructions without them is
+// recorded in profiles/gemm256_one_schedule_a_asm_identity.txt.
 //
 // Operand layouts, swizzles, swapped-operand MFMA and epilogue are those of gemm.hip.
 #include "common.hpp"
@@ -55,8 +71,6 @@ template <int NT> struct Geo {
     static constexpr int B_BYTES = BN * BK * 2;        // 32 / 40 KiB
     static constexpr int STAGE = A_BYTES + B_BYTES;
     static constexpr int LDS = 2 * STAGE;              // 128 / 144 KiB
-    static constexpr int PA = A_BYTES / 1024 / 8;      // DMA pieces per wave per tile (A): 4
-    static constexpr int PB = B_BYTES / 1024 / 8;      // (B): 4 / 5
 };
 
 // Swizzle of the k-strided image (XOR on the 16-B chunk index of k-row `krow`; bit 0 untouched so a 32-B block of
@@ -71,45 +85,29 @@ __device__ __forceinline__ uint32_t trswz2(uint32_t krow) {
     return (((krow >> 1) & 1) | (((krow >> 3) & 1) << 1)) << 1;
 }
 
-// loop-invariant part of one DMA piece: byte offset of this lane's 16-B chunk at k-tile 0 (or OOB).  The source chunk index
-// inside the 64-wide k-tile that the ragged-K check of a row-mode piece needs is the same for every piece of a wave
-// (pieces are 8 rows apart per wave step of 8 or 4, and the swizzle looks at (row >> 1) & 7): piece_kchunk().
-struct Piece { uint32_t voff; };
-__device__ __forceinline__ uint32_t piece_kchunk(int wave, int lane) { return swz128(wave * 8 + (lane >> 3), lane & 7); }
-
+// loop-invariant part of one DMA piece (1 KiB of an LDS image): byte offset of this lane's 16-B chunk at k-tile 0 (or OOB).
 template <bool KSTRIDED, int ROWS_OR_COLS>
-__device__ __forceinline__ Piece make_piece(int piece, int lane, int ld, int idx0, int idx_max) {
-    Piece pc;
+__device__ __forceinline__ uint32_t make_piece(int piece, int lane, int ld, int idx0, int idx_max) {
     if (!KSTRIDED) {
         const int r = piece * 8 + (lane >> 3);
         const int c = swz128(r, lane & 7);
         const int gi = idx0 + r;
-        pc.voff = gi < idx_max ? (uint32_t)(((int64_t)gi * ld + c * 8) * 2) : YAT_OOB;
+        return gi < idx_max ? (uint32_t)(((int64_t)gi * ld + c * 8) * 2) : YAT_OOB;
     } else {
         constexpr int ROWB = ROWS_OR_COLS * 2;                 // bytes per k-row of the LDS image
         const uint32_t o = piece * 1024 + lane * 16;
         const uint32_t r = o / ROWB, slot = (o % ROWB) >> 4;
         const uint32_t c = slot ^ trswz2<ROWS_OR_COLS>(r);
         const int gi = idx0 + c * 8;
-        pc.voff = gi < idx_max ? (uint32_t)(((int64_t)r * ld + gi) * 2) : YAT_OOB;   // k-rows past K: buffer range check
+        return gi < idx_max ? (uint32_t)(((int64_t)r * ld + gi) * 2) : YAT_OOB;   // k-rows past K: buffer range check
     }
-    return pc;
 }
 
-template <bool KSTRIDED, int COLS>
+// fragment of the k-contiguous A image (128-B rows, swz128): rows idx0 .. idx0 + 15, 32-deep half kk
 __device__ __forceinline__ bf16x8 frag256(const char* lds, int idx0, int kk, int lane) {
-    if (!KSTRIDED) {
-        const uint32_t r = idx0 + (lane & 15);
-        const uint32_t c = swz128(r, kk * 4 + (lane >> 4));
-        return lds_read8(lds, r * 128 + c * 16);
-    } else {
-        constexpr uint32_t ROWB = COLS * 2;
-        const uint32_t g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-        const uint32_t col = idx0 + 4 * p;
-        const uint32_t r0 = kk * 32 + 8 * g + q, r1 = r0 + 4;
-        const uint32_t c0 = (col >> 3) ^ trswz2<COLS>(r0), c1 = (col >> 3) ^ trswz2<COLS>(r1);
-        return cat4(lds_read_tr4(lds, r0 * ROWB + c0 * 16 + (p & 1) * 8), lds_read_tr4(lds, r1 * ROWB + c1 * 16 + (p & 1) * 8));
-    }
+    const uint32_t r = idx0 + (lane & 15);
+    const uint32_t c = swz128(r, kk * 4 + (lane >> 4));
+    return lds_read8(lds, r * 128 + c * 16);
 }
 
 // The k-strided fragment addresses, arranged so a LOAD segment computes almost nothing.  A lane reads rows r0 = 32 kk + 8 g + q
@@ -141,11 +139,6 @@ __device__ __forceinline__ bf16x4 lds_read_tr4_asm(uint32_t lds_addr) {
 template <int COLS>
 __device__ __forceinline__ bf16x8 frag_tr(uint32_t lds_addr, int kk) {
     constexpr int R4 = 4 * COLS * 2, K1 = 32 * COLS * 2;
-#ifdef YAT_GEMM_TR_BUILTIN          // A/B only: the builtin form with the compiler's conservative vmcnt(0)
-    YAT_LDS const char* a = (YAT_LDS const char*)(uintptr_t)lds_addr;
-    return cat4(__builtin_amdgcn_ds_read_tr16_b64_v4bf16((YAT_LDS bf16x4*)(a + kk * K1)),
-                __builtin_amdgcn_ds_read_tr16_b64_v4bf16((YAT_LDS bf16x4*)(a + kk * K1 + R4)));
-#endif
     if (kk == 0) return cat4(lds_read_tr4_asm<0>(lds_addr), lds_read_tr4_asm<R4>(lds_addr));
     return cat4(lds_read_tr4_asm<K1>(lds_addr), lds_read_tr4_asm<K1 + R4>(lds_addr));
 }
@@ -156,37 +149,6 @@ __device__ __forceinline__ bf16x8 frag_tr(uint32_t lds_addr, int kk) {
         __builtin_amdgcn_s_barrier();        \
         __builtin_amdgcn_sched_barrier(0);   \
     } while (0)
-
-// Diagnostic builds only (scripts/build_variant.py ... -DYAT_ABL_*; results are then WRONG, only the time is read): where
-// does the main loop's time go -- waiting for the LDS-DMA to land, issuing it, or the four rendezvous per K-tile?
-#ifdef YAT_ABL_NO_BARRIER
-#define YAT_LOOP_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#else
-#define YAT_LOOP_BARRIER() YAT_PHASE_BARRIER()
-#endif
-#ifdef YAT_ABL_NO_LDSREAD
-#define YAT_ABL_SKIP_READS 1
-#else
-#define YAT_ABL_SKIP_READS 0
-#endif
-
-// Diagnostic build -DYAT_GEMM_STAMPS (scripts/gemm_stamps.py): every wave of workgroup 0 sums, per K-loop iteration slot, the
-// s_memtime ticks it spent in  [4 kk + 0] LOAD (fragment reads issued and landed, incl. its DMA wait)  [+1] the rendezvous
-// after it  [+2] COMPUTE (MFMA + DMA issue)  [+3] the rendezvous after it (incl. group 0's DMA wait).  The sums go to a
-// buffer of their own that nothing else reads; the product build contains none of this.
-#ifdef YAT_GEMM_STAMPS
-__device__ unsigned int yat_gemm_stamp_buf[8 * 8 + 8];
-#define YAT_STAMP(slot)                                                       \
-    do {                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                    \
-        const uint32_t now_ = (uint32_t)__builtin_amdgcn_s_memtime();         \
-        st_sum[slot] += now_ - st_prev;                                       \
-        st_prev = now_;                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                    \
-    } while (0)
-#else
-#define YAT_STAMP(slot) do {} while (0)
-#endif
 
 // workgroups are dealt round-robin to the 8 XCDs: give every XCD one contiguous run of `nwg` work items
 __device__ __forceinline__ int xcd_contiguous(int nwg) {
@@ -201,19 +163,13 @@ template <bool A_T, bool B_T, int NT, int EPI = 0>      // EPI: 0 standard, 1 GL
 __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
     using G = Geo<NT>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef YAT_GEMM_STAMPS
-    const uint32_t st_kernel_begin = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = wave >> 2, wc = wave & 3;
 
     const int ksl = id % p.ksplit;             // K slice of this workgroup (slices of one tile are neighbours -> same XCD)
     id /= p.ksplit;
-#ifndef YAT_GEMM_GROUP
-#define YAT_GEMM_GROUP 4
-#endif
-    const int GROUP = p.group > 0 ? p.group : YAT_GEMM_GROUP;
+    const int GROUP = p.group > 0 ? p.group : 4;
     const int per_group = GROUP * p.nbn;
     const int gid = id / per_group, first_m = gid * GROUP;
     const int gsz = min(p.nbm - first_m, GROUP);
@@ -230,13 +186,6 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
     const __amdgpu_buffer_rsrc_t ra2 = make_rsrc(EPI == 5 ? p.A2 + a2_col : p.A, EPI == 5 ? p.a2_bytes - (uint64_t)a2_col * 2 : 0);
     const __amdgpu_buffer_rsrc_t rb2 = make_rsrc(EPI == 5 ? p.B2 : p.B, EPI == 5 ? p.b2_bytes : 0);
 
-    // this wave's DMA pieces (loop invariant): A pieces wave + 8j, B pieces wave + 8j
-    Piece pa[G::PA], pb[G::PB];
-#pragma unroll
-    for (int j = 0; j < G::PA; ++j) pa[j] = make_piece<A_T, BM>(wave + 8 * j, lane, p.lda, m0, p.M);
-#pragma unroll
-    for (int j = 0; j < G::PB; ++j) pb[j] = make_piece<B_T, G::BN>(wave + 8 * j, lane, p.ldb, n0, p.N);
-    const uint32_t kchunk = piece_kchunk(wave, lane);
     const uint32_t a_kstep = A_T ? (uint32_t)(BK * p.lda * 2) : (uint32_t)(BK * 2);
     const uint32_t b_kstep = B_T ? (uint32_t)(BK * p.ldb * 2) : (uint32_t)(BK * 2);
     const int nt_main = (p.K + BK - 1) / BK;
@@ -260,46 +209,6 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
     // last tile unless a second operand pair follows it)
     const int tail_at = ragged ? nt_main - 1 - kt0 : nt;
     const int nfull = (tail_at >= 0 && tail_at < nt) ? tail_at : nt;
-    auto piece = [&](auto checked, int tl, char* stage, int j) {
-        constexpr bool CHECKED = decltype(checked)::value;
-        const int t = ktile(tl);
-        const bool opa = j < G::PA;
-        const int jj = opa ? j : j - G::PA;
-        if (opa) {
-            YAT_LDS void* dst = (YAT_LDS void*)(stage + (wave + 8 * jj) * 1024);
-            if (CHECKED) {
-                const uint32_t kvalid = (uint32_t)(p.K - t * BK) >> 3;     // valid 16-B chunks in this k-tile (row-mode)
-                uint32_t v = pa[jj].voff + (uint32_t)t * a_kstep;
-                if (!A_T && kchunk >= kvalid) v = YAT_OOB;
-                lds_dma16(ra, dst, v);
-            } else {
-                lds_dma16s(ra, dst, pa[jj].voff, (uint32_t)t * a_kstep);
-            }
-        } else {
-            YAT_LDS void* dst = (YAT_LDS void*)(stage + G::A_BYTES + (wave + 8 * jj) * 1024);
-            if (CHECKED) {
-                const uint32_t kvalid = (uint32_t)(p.K - t * BK) >> 3;
-                uint32_t v = pb[jj].voff + (uint32_t)t * b_kstep;
-                if (!B_T && kchunk >= kvalid) v = YAT_OOB;
-                lds_dma16(rb, dst, v);
-            } else {
-                lds_dma16s(rb, dst, pb[jj].voff, (uint32_t)t * b_kstep);
-            }
-        }
-    };
-    constexpr int NPIECE = G::PA + G::PB;        // 8 or 9 pieces per wave per tile
-    auto issue_range = [&](int tl, char* stage, int j0, int j1) {       // pieces [j0, j1) of tile tl, form chosen once
-        if (is_tail(tl)) {
-#pragma unroll
-            for (int j = 0; j < NPIECE; ++j)
-                if (j >= j0 && j < j1) piece(std::true_type{}, tl, stage, j);
-        } else {
-#pragma unroll
-            for (int j = 0; j < NPIECE; ++j)
-                if (j >= j0 && j < j1) piece(std::false_type{}, tl, stage, j);
-        }
-    };
-    auto issue = [&](int tl, char* stage) { issue_range(tl, stage, 0, NPIECE); };
 
     f32x4 acc[8][NT];
 #pragma unroll
@@ -317,11 +226,6 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) racc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-#ifdef YAT_GEMM_STAMPS
-    uint32_t st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t st_prev = 0;
-    int st_slot = 0;
-#endif
     // per-lane LDS addresses of the k-strided fragments (tr_lane_addr above): one for A, one (256-column) or NT for B
     const uint32_t lds0 = (uint32_t)(uintptr_t)(YAT_LDS char*)smem;
     uint32_t a_tr[1] = {0}, b_tr[NT == 4 ? 1 : NT] = {0};
@@ -331,102 +235,19 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) b_tr[j] = tr_lane_addr<G::BN>(wc * 16 * NT + j * 16, lane);
     }
-    // COMPUTE segment: 8 x NT MFMAs on registers; when dma_tile >= 0 this wave's DMA pieces for that tile are
-    // issued between groups of 4 MFMAs (the matrix pipe keeps draining queued MFMAs while the wave issues a DMA),
-    // so the LOAD segments carry only the fragment reads and stay shorter than the partner's COMPUTE segment.
-#ifndef YAT_GEMM_DIC_ALL
-#define YAT_GEMM_DIC_ALL 0          // 1: measured +4..6 % on the forward shapes alone, but the step got 2.4 ms SLOWER
-#endif
-    constexpr bool DIC_ = A_T || B_T || YAT_GEMM_DIC_ALL;
-    // One piece every GAP MFMAs from the start of the segment (2 or 4: no measurable difference once the transposing reads
-    // stopped waiting for the DMA, see frag_tr).
-#ifndef YAT_GEMM_GAP
-#define YAT_GEMM_GAP 2
-#endif
-    constexpr int GAP = YAT_GEMM_GAP;      // 256 x 192 tile: 24 MFMAs carry 7 pieces -> one every 3
-    static_assert((8 * NT) / GAP >= NPIECE, "not enough MFMA slots for the DMA pieces of a tile");
-    // MODE 0: no DMA in this segment; 1: scalar-offset pieces, unconditionally (two scalar instructions + the DMA each);
-    // 2: decided per piece at run time (tile missing / ragged last k-tile) -- only in the last iterations of a K loop
-    // The rendezvous that ends the segment is executed EARLY MFMAs before its end: the partner group, parked at the end of
-    // its LOAD segment, is released while this wave's last MFMAs are still in the pipe, so the barrier's turnaround overlaps
-    // them instead of idling the matrix pipe.  Legal because a COMPUTE segment touches registers only (every LDS read
-    // retired before the barrier that ends the LOAD segment) and the DMA waits move with the barrier.
-#ifndef YAT_GEMM_EARLY
-#define YAT_GEMM_EARLY 0
-#endif
-    constexpr int EARLY = YAT_GEMM_EARLY;
-    auto compute = [&](auto mode_c, int dma_tile, bool wait_dma) {
-        constexpr int MODE = decltype(mode_c)::value;
-        char* dst = smem + (dma_tile & 1) * G::STAGE;
-        const bool checked = MODE == 2 && dma_tile >= 0 && is_tail(dma_tile);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                acc[i][j] = mfma16(bfr[j], af[i], acc[i][j]);   // D[n][m]
-                const int idx = i * NT + j;
-                if (MODE != 0 && idx % GAP == GAP - 1 && idx / GAP < NPIECE) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (MODE == 1) piece(std::false_type{}, dma_tile, dst, idx / GAP);
-                    else if (dma_tile >= 0) {
-                        if (checked) piece(std::true_type{}, dma_tile, dst, idx / GAP);
-                        else piece(std::false_type{}, dma_tile, dst, idx / GAP);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if (EPI == 4 && idx == 8 * NT - 1 && rs_wave) {
-                    bf16x8 ones;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) racc[q] = mfma16(ones, af[q], racc[q]);
-                }
-                if (idx == 8 * NT - 1 - EARLY) {
-                    YAT_STAMP(st_slot);
-#ifndef YAT_ABL_NO_VMWAIT
-                    if (wait_dma) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // tile t+1 (group 0's pieces)
-#endif
-                    YAT_LOOP_BARRIER();
-                }
-            }
-        }
-        __builtin_amdgcn_s_setprio(0);
-    };
+    // A COMPUTE segment issues one DMA piece every GAP MFMAs from its start: the matrix pipe keeps draining queued MFMAs
+    // while the wave issues a DMA, so the LOAD segments carry only the fragment reads and stay shorter than the partner's
+    // COMPUTE segment.  (2 or 4: no measurable difference once the transposing reads stopped waiting for the DMA, see frag_tr.)
+    constexpr int GAP = 2;
 
-    // Where the DMA issue goes is a measured choice (gemm micro-benchmark, SANA shapes): with both operands
-    // k-contiguous the load segment is short (12-13 ds_read_b128) and absorbs the issue for free, while DMA between
-    // MFMAs costs 15-20 %; with a k-strided operand (twice the LDS read instructions + swizzle arithmetic) the load
-    // segment is the long pole and the issue belongs in the compute segment (+12..20 %).
-    constexpr bool DIC = DIC_;                 // DMA In Compute segment (group 0; group 1 too unless stated otherwise)
-#ifndef YAT_GEMM_NT_G1C
-#define YAT_GEMM_NT_G1C 0
-#endif
-    constexpr bool DIC_G1 = DIC || YAT_GEMM_NT_G1C;   // group 1 alone may prefetch tile t+2 from COMPUTE(t,ks1)
-
-#ifndef YAT_GEMM_DEEP
-#define YAT_GEMM_DEEP 1
-#endif
-#ifndef YAT_GEMM_PIN_WAIT
-#define YAT_GEMM_PIN_WAIT 1
-#endif
-#ifndef YAT_GEMM_DEEP_KH
-#define YAT_GEMM_DEEP_KH 1          // the DEEP schedule for a k-contiguous B operand too (round 5: half-major B image, below)
-#endif
-#ifdef YAT_GEMM_STAMPS
-    constexpr bool DEEP = false;                           // (the stamp slots describe the two-stage schedule)
-#else
-    constexpr bool DEEP = YAT_GEMM_DEEP && (B_T || YAT_GEMM_DEEP_KH);
-#endif
-    static_assert(EPI != 5 || DEEP, "the second operand pair is wired into the DEEP loop's DMA only");
-    // B image of a DEEP kernel with a k-contiguous B operand (the forward GEMMs: B = W[N, K]).  The row image of the two-stage
-    // schedule keeps both 32-deep halves of a column in one 128-B row, so no half can be refilled before the other has been
-    // read.  Here the image is HALF-MAJOR: [half h][column n][4 chunks of 16 B] -- 64-B rows, half h at h * 64 * BN bytes --
-    // which makes it piece for piece the shape of the k-strided image (1 KiB = 16 columns of one half; BN / 16 pieces per
-    // half), so the DEEP loop, its batches and its counted waits carry over unchanged.  Chunk c of column n sits at slot
+    // B image of a k-contiguous B operand (the forward GEMMs: B = W[N, K]).  A row image like A's would keep both 32-deep
+    // halves of a column in one 128-B row, so no half could be refilled before the other has been read.  Here the image is
+    // HALF-MAJOR: [half h][column n][4 chunks of 16 B] -- 64-B rows, half h at h * 64 * BN bytes -- which makes it piece for
+    // piece the shape of the k-strided image (1 KiB = 16 columns of one half; BN / 16 pieces per half), so the loop, its
+    // batches and its counted waits are the same for both B layouts.  Chunk c of column n sits at slot
     // c ^ kh_perm((n >> 2) & 3): the 16 lanes one ds_read_b128 services together (MI355X_MICROARCH.md, LDS) read columns
     // {0..3, 12..15} of one chunk and {4..11} of its neighbour and land on 16 distinct 16-B slots of the 256-B bank row.
-    constexpr bool B_KH = DEEP && !B_T;
+    constexpr bool B_KH = !B_T;
     auto kh_perm = [](uint32_t x) { return (0x78u >> (2 * x)) & 3u; };          // 0, 2, 3, 1
     const uint32_t kh_lane = ((uint32_t)(lane & 15) * 64) + ((((uint32_t)lane >> 4) ^ kh_perm((lane & 15) >> 2)) << 4);
 
@@ -441,7 +262,7 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
             for (int i = 0; i < 8; ++i) af[i] = frag_tr<BM>(a0 ^ (i << 5), kk);
         } else {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) af[i] = frag256<false, BM>(cur, GRP * 128 + i * 16, kk, lane);
+            for (int i = 0; i < 8; ++i) af[i] = frag256(cur, GRP * 128 + i * 16, kk, lane);
         }
         if (B_T && NT == 4) {
             const uint32_t b0 = b_tr[0] + st + G::A_BYTES;
@@ -450,21 +271,19 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
         } else if (B_T) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) bfr[j] = frag_tr<G::BN>(b_tr[j] + st + G::A_BYTES, kk);
-        } else if (B_KH) {
+        } else {                                                     // (B_KH: the half-major image)
             const char* b0 = cur + G::A_BYTES + kk * (G::B_BYTES / 2) + wc * (16 * NT * 64) + kh_lane;
 #pragma unroll
             for (int j = 0; j < NT; ++j) bfr[j] = lds_read8(b0, j * 1024);
-        } else {
-#pragma unroll
-            for (int j = 0; j < NT; ++j) bfr[j] = frag256<false, G::BN>(cur + G::A_BYTES, wc * 16 * NT + j * 16, kk, lane);
         }
     };
 
-#ifdef YAT_GEMM_STAMPS
-    uint32_t st_loop_begin = 0;
-#endif
-    if constexpr (DEEP) {
-      auto deep_loop = [&](auto grp_c) {
+    // The K loop of one wave group (GRP a constant: which batches a segment carries and what its waits count is decided at
+    // compile time).  The loop body exists as a FAST form -- every batch of the wait window was issued in full and none of its
+    // tiles is the ragged one, so its pieces are unconditional scalar-offset DMAs and its waits are counted -- plus the general
+    // form (per-piece tile checks, vmcnt(0)) for the last iterations.  Both groups execute the same number of barriers per
+    // iteration in either form.
+    auto k_loop = [&](auto grp_c) {
         constexpr int GRP = decltype(grp_c)::value;
         constexpr int NB = (NT == 5 && GRP == 1) ? 3 : 2;    // B pieces per half and wave (320 columns: 20 = 4 x 2 + 4 x 3)
         constexpr int NAH = A_T ? 2 : 0;                      // k-strided A: pieces per half and wave
@@ -474,7 +293,7 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
         // chosen a whole number of swizzle periods apart (16 or 32 k-rows of a k-strided image, 32 rows of a k-contiguous
         // one): their per-lane offsets then differ by a wave-uniform number of rows, so ONE per-lane offset per operand (two
         // for the odd piece of group 1 in the 320-column image) serves them all and the row delta rides, with the K-tile
-        // advance, in the instruction's scalar offset -- 2..3 address registers where the two-stage schedule keeps 9.
+        // advance, in the instruction's scalar offset -- 2..3 address registers instead of one per piece (9).
         //   k-strided 256-column image (A; B of the 256-wide tile): piece = wave + 8 i + 16 h   -> k-row delta 16 i + 32 h
         //   k-strided 320-column image: 20 pieces per half = classes {q, q + 10}; group 0 wave wc: class wc; group 1 wave wc:
         //                               class 4 + wc and one piece of classes 8 / 9 (8, 18, 9, 19)       -> deltas 16 i + 32 h
@@ -482,17 +301,17 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
         const int pa0 = A_T ? wave : 16 * GRP + wc;
         const int pb0 = NT == 4 ? wave : (GRP ? 4 + wc : wc);
         const int pbx = 8 + (wc >> 1) + 10 * (wc & 1);                     // (320 columns, group 1: 8, 18, 9, 19)
-        const uint32_t va0 = make_piece<A_T, BM>(pa0, lane, p.lda, m0, p.M).voff;
+        const uint32_t va0 = make_piece<A_T, BM>(pa0, lane, p.lda, m0, p.M);
         // (k-contiguous A: the pieces of a wave are 32 ROWS of M apart, and a scalar-offset delta is outside the buffer range
         // check -- past the last row of a ragged M it would read beyond the operand.  They keep their own per-lane offsets,
         // each with make_piece's row check.)
         uint32_t vao[A_T ? 1 : 4];
         if (!A_T) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) vao[j] = j == 0 ? va0 : make_piece<false, BM>(pa0 + 4 * j, lane, p.lda, m0, p.M).voff;
+            for (int j = 0; j < 4; ++j) vao[j] = j == 0 ? va0 : make_piece<false, BM>(pa0 + 4 * j, lane, p.lda, m0, p.M);
         }
-        const uint32_t vb0 = B_KH ? 0 : make_piece<true, G::BN>(pb0, lane, p.ldb, n0, p.N).voff;
-        const uint32_t vbx = (NB == 3 && !B_KH) ? make_piece<true, G::BN>(pbx, lane, p.ldb, n0, p.N).voff : 0;
+        const uint32_t vb0 = B_KH ? 0 : make_piece<true, G::BN>(pb0, lane, p.ldb, n0, p.N);
+        const uint32_t vbx = (NB == 3 && !B_KH) ? make_piece<true, G::BN>(pbx, lane, p.ldb, n0, p.N) : 0;
         // half-major k-contiguous B image (B_KH): piece q of half h = the 64-B half rows of columns 16 q .. 16 q + 15.  The
         // pieces of a wave are 128 or 160 COLUMNS of N apart, and a scalar-offset delta is outside the buffer range check (past
         // the last column of a ragged N it would read beyond the operand): each keeps its own per-lane offset with its own column
@@ -573,7 +392,7 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
             if (decltype(fast_c)::value) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         };
-        auto compute_deep = [&](auto kk_c, auto fast_c, int t) {
+        auto compute = [&](auto kk_c, auto fast_c, int t) {
             constexpr int KK = decltype(kk_c)::value;
             constexpr int NP = batch_count(KK);
             static_assert((8 * NT) / GAP >= NP, "not enough MFMA slots for the DMA pieces of a batch");
@@ -600,9 +419,7 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
                         // (the counted wait is an asm the scheduler may hoist over the register-only MFMAs -- it did, to right
                         // behind the segment's last piece, giving up a segment of landing time: pinned behind them)
                         if (GRP == 0) {
-#if YAT_GEMM_PIN_WAIT
                             __builtin_amdgcn_sched_barrier(0);
-#endif
                             wait_g0(fast_c);
                         }
                         YAT_PHASE_BARRIER();
@@ -611,19 +428,19 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
             }
             __builtin_amdgcn_s_setprio(0);
         };
-        auto iteration_deep = [&](auto fast_c, int t) {
+        auto iteration = [&](auto fast_c, int t) {
             // ---- sub-step 0
             load_frags(grp_c, t, 0);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (GRP == 1) wait_g1(std::integral_constant<int, 0>{}, fast_c);
             YAT_PHASE_BARRIER();
-            compute_deep(std::integral_constant<int, 0>{}, fast_c, t);
+            compute(std::integral_constant<int, 0>{}, fast_c, t);
             // ---- sub-step 1
             load_frags(grp_c, t, 1);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (GRP == 1) wait_g1(std::integral_constant<int, 1>{}, fast_c);
             YAT_PHASE_BARRIER();
-            compute_deep(std::integral_constant<int, 1>{}, fast_c, t);
+            compute(std::integral_constant<int, 1>{}, fast_c, t);
         };
 
         // prologue: tile 0 in full (every wave its own pieces), then the batches a running loop would have issued for tile 1:
@@ -655,139 +472,11 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
 
         const int nfast = max(0, nfull - 2);
         int t = 0;
-        for (; t < nfast; ++t) iteration_deep(std::true_type{}, t);
-        for (; t < nt; ++t) iteration_deep(std::false_type{}, t);
-      };
-      if (grp == 0) deep_loop(std::integral_constant<int, 0>{});
-      else deep_loop(std::integral_constant<int, 1>{});
-    } else {
-
-    issue(0, smem);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    YAT_PHASE_BARRIER();                       // rendezvous 0: tile 0 visible to everyone
-    if (grp == 1) {
-        // (DIC) group 1 issues tile t+2 inside its COMPUTE(t, ks1), so its share of tile 1 goes out here
-        if (DIC_G1 && nt > 1) issue(1, smem + G::STAGE);
-        YAT_PHASE_BARRIER();                   // stagger: group 1 runs one segment behind group 0
-    }
-
-    // DMA protocol (n-th barrier of every wave is one rendezvous; group 0's iteration t spans 4t+1..4t+4, group 1's
-    // 4t+2..4t+5).  Tile u lives in stage u&1 and is first read after rendezvous 4u.
-    //   group 0 issues its pieces of tile t+1 in COMPUTE(t,ks0)  [after 4t+1 > 4t: stage free] and waits for them
-    //           before its 4th barrier of iteration t (= 4t+4);
-    //   group 1 issues its pieces of tile t+2 in COMPUTE(t,ks1)  [after 4t+4: every read of tile t retired] and waits
-    //           for tile t+1's pieces before its 3rd barrier of iteration t (= 4t+4).
-    //   (!DIC) every wave issues tile t+1 at the top of LOAD(t,ks0) [after its 4th barrier of iteration t-1 >= 4t]
-    //           and waits before its 3rd barrier of iteration t (<= 4t+4).
-    // The loop body exists per wave group (GRP a constant: which segment carries the DMA is then decided at compile time)
-    // and as a FAST form -- the tile this iteration fetches exists and is a full one, so its pieces are unconditional,
-    // scalar-offset DMAs with no branch and no VALU around them -- plus the general form for the last iterations.  Both
-    // groups execute the same number of barriers per iteration in either form.
-    auto iteration = [&](auto grp_c, auto fast_c, int t) {
-        constexpr int GRP = decltype(grp_c)::value;
-        constexpr bool dic = GRP == 0 ? DIC : DIC_G1;      // does THIS group issue its DMA from a compute segment?
-        constexpr bool FAST = decltype(fast_c)::value;
-        const char* cur = smem + (t & 1) * G::STAGE;
-        // (!DIC) pieces of tile t+1 issued at the top of LOAD(t,ks0); group 0 may keep the last NPIECE - H0 of them for the top
-        // of its LOAD(t,ks1) -- it then waits after COMPUTE(t,ks1) like a DIC kernel's group 0 (YAT_GEMM_NT_SPLIT)
-#ifndef YAT_GEMM_NT_SPLIT
-#define YAT_GEMM_NT_SPLIT 99
-#endif
-        const bool g0split = !dic && GRP == 0 && YAT_GEMM_NT_SPLIT < NPIECE;
-        const int H0 = g0split ? YAT_GEMM_NT_SPLIT : NPIECE;
-        char* nxt = smem + ((t + 1) & 1) * G::STAGE;
-        // (!dic) YAT_GEMM_NT_READS_FIRST=1 puts the pieces AFTER the fragment reads of LOAD(t,ks0) (the reads then do not queue
-        // behind nine pieces): +3..4 % on the forward shapes alone, 84.4 -> 84.6 ms in the step (both orders) -- off.
-#ifndef YAT_GEMM_NT_READS_FIRST
-#define YAT_GEMM_NT_READS_FIRST 0
-#endif
-        auto nt_issue = [&]() {
-#ifndef YAT_ABL_NO_DMA
-            if (!dic) {
-                if (FAST) {
-#pragma unroll
-                    for (int j = 0; j < NPIECE; ++j)
-                        if (j < H0) piece(std::false_type{}, t + 1, nxt, j);
-                } else if (t + 1 < nt) {
-                    issue_range(t + 1, nxt, 0, H0);
-                }
-            }
-#endif
-        };
-        if (!YAT_GEMM_NT_READS_FIRST) nt_issue();
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            // ---- LOAD segment
-#ifndef YAT_ABL_NO_DMA
-            if (g0split && kk == 1) {
-                if (FAST) {
-#pragma unroll
-                    for (int j = 0; j < NPIECE; ++j)
-                        if (j >= H0) piece(std::false_type{}, t + 1, nxt, j);
-                } else if (t + 1 < nt) {
-                    issue_range(t + 1, nxt, H0, NPIECE);
-                }
-            }
-#endif
-#ifdef YAT_GEMM_LOADPRIO
-            __builtin_amdgcn_s_setprio(YAT_GEMM_LOADPRIO);
-#endif
-            if (!YAT_ABL_SKIP_READS || t == 0) load_frags(grp_c, t, kk);
-            if (YAT_GEMM_NT_READS_FIRST && kk == 0) {
-                __builtin_amdgcn_sched_barrier(0);
-                nt_issue();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifndef YAT_ABL_NO_VMWAIT
-            if (kk == 1 && ((!dic && !g0split) || GRP == 1)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile t+1 landed
-#endif
-            YAT_STAMP(4 * kk + 0);
-            YAT_LOOP_BARRIER();
-            YAT_STAMP(4 * kk + 1);
-            // ---- COMPUTE segment: group 0 carries its DMA (tile t+1) in ks0, group 1 (tile t+2) in ks1
-#ifdef YAT_ABL_NO_DMA
-            compute(std::integral_constant<int, 0>{}, 0, false);
-#else
-#ifdef YAT_GEMM_STAMPS
-            st_slot = 4 * kk + 2;
-#endif
-            const int tile = t + 1 + GRP;
-            const bool wd = (dic || g0split) && kk == 1 && GRP == 0;                               // group 0 waits for its pieces of tile t+1
-            if (dic && kk == GRP) {
-                if (FAST) compute(std::integral_constant<int, 1>{}, tile, wd);
-                else compute(std::integral_constant<int, 2>{}, tile < nt ? tile : -1, wd);
-            } else {
-                compute(std::integral_constant<int, 0>{}, 0, wd);
-            }
-#endif
-            YAT_STAMP(4 * kk + 3);
-        }
+        for (; t < nfast; ++t) iteration(std::true_type{}, t);
+        for (; t < nt; ++t) iteration(std::false_type{}, t);
     };
-    auto k_loop = [&](auto grp_c) {
-        // iterations whose fetched tile (t+1; t+2 for group 1 of a DIC kernel) exists and is not the ragged last one
-        const int ahead = (grp_c.value == 0 ? DIC : DIC_G1) ? 1 + grp_c.value : 1;
-        const int nfast = max(0, nfull - ahead);
-        int t = 0;
-        for (; t < nfast; ++t) iteration(grp_c, std::true_type{}, t);
-        for (; t < nt; ++t) iteration(grp_c, std::false_type{}, t);
-    };
-#ifdef YAT_GEMM_STAMPS
-    st_prev = (uint32_t)__builtin_amdgcn_s_memtime();
-    st_loop_begin = st_prev;
-#endif
     if (grp == 0) k_loop(std::integral_constant<int, 0>{});
     else k_loop(std::integral_constant<int, 1>{});
-    }   // (!DEEP)
-#ifdef YAT_GEMM_STAMPS
-    const uint32_t st_loop_end = (uint32_t)__builtin_amdgcn_s_memtime();
-    if (blockIdx.x == 0 && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) yat_gemm_stamp_buf[wave * 8 + i] = st_sum[i];
-        yat_gemm_stamp_buf[64] = (unsigned)nt;
-        if (wave == 0) { yat_gemm_stamp_buf[65] = st_loop_begin - st_kernel_begin; yat_gemm_stamp_buf[66] = st_loop_end - st_loop_begin; }
-    }
-#endif
     if (grp == 0) YAT_PHASE_BARRIER();         // pair group 1's last barrier
 
     if (EPI == 4 && rs_wave && p.ksplit == 1 && (lane >> 4) == 0) {
@@ -824,12 +513,8 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
         // ahead of their use, into the registers the pass before has just emptied: read where they are consumed, each of the
         // four passes of a tile paid an HBM round trip behind its slab round trip (the gated-residual and GLU-backward GEMMs
         // ran 714 .. 990 TFLOP/s in the step).  Same loads, same arithmetic, same stores: bit-identical.
-#ifndef YAT_GEMM_EPI_PREFETCH
-#define YAT_GEMM_EPI_PREFETCH 1
-#endif
         constexpr int UPL = (32 * CPR + 63) / 64;          // 8-column units per lane and pass
-        constexpr bool HAS_IN = YAT_GEMM_EPI_PREFETCH && (EPI == 1 || EPI == 2 || EPI == 3 || EPI == 0 || EPI == 4 || EPI == 5);
-        const bool pre_on = HAS_IN && !split && (EPI == 1 || EPI == 3 || EPI == 2 || p.res != nullptr);
+        const bool pre_on = !split && (EPI == 1 || EPI == 3 || EPI == 2 || p.res != nullptr);
         // one input stream (residual | z): a whole pass ahead, double-buffered; two streams (GLU u_a + u_g, residual + pre_add):
         // the registers do not hold two passes of both -- loaded at the top of their own pass, before its slab round trip
         constexpr bool AHEAD = EPI != 1 && EPI != 2;
@@ -892,10 +577,6 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads retired before the next pass overwrites the slab
         }
-#ifdef YAT_GEMM_STAMPS
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (blockIdx.x == 0 && lane == 0 && wave == 0) yat_gemm_stamp_buf[67] = (uint32_t)__builtin_amdgcn_s_memtime() - st_loop_end;
-#endif
         return;
     }
 #pragma unroll
@@ -1054,14 +735,8 @@ int yat_gemm256_launch(int a_t, int b_t, int nt_variant, const GemmP& p, hipStre
         return launch256<true, true, 4, 4>(p, stream);
     }
     if (p.A2) {                    // second operand pair: forward layout, no split-K
-        // (wired into the DEEP loop's DMA only: the diagnostic builds without that loop for the forward layout --
-        //  -DYAT_GEMM_STAMPS, -DYAT_GEMM_DEEP=0, -DYAT_GEMM_DEEP_KH=0 -- do not instantiate EPI 5 and refuse the call)
-#if !defined(YAT_GEMM_STAMPS) && YAT_GEMM_DEEP && YAT_GEMM_DEEP_KH
         if (a_t || b_t || p.ksplit > 1) return YAT_EINVAL;
         return nt_variant == 5 ? launch256<false, false, 5, 5>(p, stream) : launch256<false, false, 4, 5>(p, stream);
-#else
-        return YAT_EINVAL;
-#endif
     }
     if (p.pre_add) {               // adapter addend: only the forward layout (x W^T) is instantiated, no split-K
         if (a_t || b_t || p.ksplit > 1) return YAT_EINVAL;
@@ -1077,9 +752,3 @@ int yat_gemm256_launch(int a_t, int b_t, int nt_variant, const GemmP& p, hipStre
 #undef YAT_CASE
     return YAT_EINVAL;
 }
-
-#ifdef YAT_GEMM_STAMPS
-extern "C" int yat_debug_gemm_stamps(unsigned int* host_dst) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(yat_gemm_stamp_buf), sizeof(unsigned int) * 72);
-}
-#endif
