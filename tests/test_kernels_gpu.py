@@ -684,6 +684,8 @@ def _glu_ref(z, wdw, bdw, B, h, w, Hc):
 #     R 16, 3 bands, bpb 3; pass 2 global-z (w < 16) R 16, 3 bands, bpb 3; last band 2 rows of 16
 #   8 x 9 x 50 x 4096 (59 MB): forward 64ch/2wg (w > 48) R 2, 5 bands, bpb 2; pass 2 band kernel R 4, 3 bands, bpb 3; last
 #     band 1 row; the last column segment 2 columns of 8
+# Every streaming shape here walks its ring one step, and where pass 1 / pass 2 walk several bands one workgroup has the whole
+# image: test_dwconv_gpu.py holds the multi-step, mid-image and ragged walks of every kernel to exact sums.
 @pytest.mark.parametrize("B,h,w,Hc", [(2, 4, 4, 16), (2, 5, 9, 40), (1, 16, 64, 160), (2, 33, 3, 8), (2, 32, 32, 72),
                                       (1, 3, 70, 8), (1, 6, 5, 12), (1, 7, 20, 40), (2, 9, 16, 64), (1, 10, 8, 24),
                                       (3, 31, 30, 136), (9, 34, 4, 8192), (8, 9, 50, 4096)])
