@@ -161,6 +161,27 @@ int yat_rmsnorm_fwd(int M, int D, float eps, const void* x, const void* w, void*
 int yat_rmsnorm_bwd(int M, int D, const void* x, const void* w, const float* rstd, const void* dy, void* dx,
                     void* dw_bf16, int accumulate_dw, void* workspace, yat_stream_t stream);
 
+/* The same RMSNorm over strided row segments: the q/k norm of SANA-1.5 (config "qk_norm": "rms_norm_across_heads").
+ * [RECALL] diffusers Attention.__init__ builds norm_q = RMSNorm(heads * dim_head, eps=1e-5) and norm_k = RMSNorm(kv_heads *
+ * dim_head, eps=1e-5) for that setting, and SanaLinearAttnProcessor2_0 / AttnProcessor2_0 apply them right after the
+ * projections (`query = attn.norm_q(query)`, `key = attn.norm_k(key)`), before the head split, the ReLU and the softmax scale.
+ *   fwd: for each of M rows, nseg (1 | 2) adjacent segments of width D (D % 8 == 0, D <= 4096): segment s reads
+ *        x + row * ldx + s * D, uses weight w<s> (w1 is read with nseg == 2 only) and writes y + row * ldy + s * D with
+ *        yat_rmsnorm_fwd's arithmetic; y may be x (in place on the q|k columns of a fused [M, 3D] projection).  keep (nullable):
+ *        the raw input, compact [M, nseg * D], for the backward.  rstd: fp32 [M, nseg].
+ *   bwd: x is the raw input (the keep buffer, or any [M, ldx] view), dy / dx strided likewise, dx may be dy.  dx carries
+ *        yat_rmsnorm_bwd's two roundings.  dw0 / dw1 (bf16 [D] each, optional accumulate): fp32 partial rows in `workspace`
+ *        (exactly yat_rmsnorm_seg_bwd_workspace_bytes(M, D, nseg) bytes), reduced in a fixed order -- no atomics.  dw0 == NULL
+ *        (and dw1 == NULL): dx only, no workspace needed (frozen base under adapters).
+ * YAT_EINVAL: D % 8, D > 4096, a leading dimension off a multiple of 8 or below nseg * D, nseg outside {1, 2}, a null
+ * operand, or only one of dw0 / dw1 with nseg == 2. */
+uint64_t yat_rmsnorm_seg_bwd_workspace_bytes(int M, int D, int nseg);
+int yat_rmsnorm_seg_fwd(int M, int D, int nseg, float eps, const void* x, int ldx, const void* w0, const void* w1, void* y,
+                        int ldy, void* keep, float* rstd, yat_stream_t stream);
+int yat_rmsnorm_seg_bwd(int M, int D, int nseg, const void* x, int ldx, const void* w0, const void* w1, const float* rstd,
+                        const void* dy, int lddy, void* dx, int lddx, void* dw0_bf16, void* dw1_bf16, int accumulate_dw,
+                        void* workspace, yat_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------ *
  * ReLU linear attention (SanaLinearAttnProcessor2_0, imported patch_sana_attention_layers.py:7)
  * qkv: bf16 [B*N, ld] with q at column 0, k at column k_off, v at column v_off, heads of dim 32

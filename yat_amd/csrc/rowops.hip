@@ -319,6 +319,150 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(int M, int D, const bf
     }
 }
 
+// ------------------------------------------------------------------ RMSNorm over strided row segments (q/k norm)
+// One wave owns one (row, segment): segment s of row r starts at x + r * ldx + s * D and has its own weight.  The segment is
+// in registers before the first store, so y may be x (in place on the q|k columns of a fused projection); `keep` (nullable)
+// receives the raw values compactly, [M, nseg * D], for the backward.  Arithmetic and rounding points: rmsnorm_fwd_kernel.
+template <int MAXV>
+__global__ __launch_bounds__(256) void rmsnorm_seg_fwd_kernel(int M, int D, int nseg, float eps, const bf16_t* x, int ldx,
+                                                              const bf16_t* w0, const bf16_t* w1, bf16_t* y, int ldy,
+                                                              bf16_t* keep, float* rstd_out) {
+    // product and sum stay two roundings, as rmsnorm_fwd_kernel is compiled: rstd is then the plain kernel's bit for bit
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t task = (int64_t)blockIdx.x * WAVES + wave;
+    if (task >= (int64_t)M * nseg) return;
+    const int64_t row = task / nseg;
+    const int seg = (int)(task - row * nseg);
+    const bf16_t* w = seg ? w1 : w0;
+    const int nchunk = D >> 3;
+    float v[MAXV][8];
+    load_row<MAXV>(x + row * ldx + (int64_t)seg * D, nchunk, lane, v);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { const float sq = v[i][e] * v[i][e]; q += sq; }
+    const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
+    if (lane == 0) rstd_out[task] = rstd;
+    bf16_t* yr = y + row * ldy + (int64_t)seg * D;
+    bf16_t* kr = keep ? keep + task * D : nullptr;          // [M, nseg * D]: (row * nseg + seg) * D
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nchunk) {
+            float ww[8], o[8];
+            unpack8(*reinterpret_cast<const u32x4*>(w + c * 8), ww);
+            if (kr) *reinterpret_cast<u32x4*>(kr + c * 8) = pack8(v[i]);      // (bf16 -> fp32 -> bf16: the same bits)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = rbf(v[i][e] * rstd) * ww[e];
+            *reinterpret_cast<u32x4*>(yr + c * 8) = pack8(o);
+        }
+    }
+}
+
+// grid = (seg_bwd_blocks(M), nseg); a workgroup strides over the 16-row groups, a wave walks ROWS_PER_WAVE rows of each like
+// rmsnorm_bwd_kernel (same two roundings); dx may be dy (the row's dy is in registers before the first store).  The fused
+// multiply-adds are written out: left to the compiler, the <.., false> instantiation (rows unrolled four times) summed
+// gg * xn as a packed multiply and an add where <.., true> used a fused one, and the dx of the two differed in the last bit.  DW: the four
+// waves' column sums meet in LDS in wave order and leave ONE partial row per workgroup, ws[seg][blk][D] -- at the step's
+// 8192 rows the 2048 per-wave rows of rmsnorm_bwd_kernel's scheme made the follow-up reduction (18 MB per segment through 35
+// workgroups, 110 us) dearer than this kernel.
+constexpr int SEG_BWD_MAX_BLOCKS = 256;          // one workgroup per CU; 1024 waves x 2 rows of loads in flight
+inline int seg_bwd_blocks(int M) {
+    const int groups = (M + WAVES * ROWS_PER_WAVE - 1) / (WAVES * ROWS_PER_WAVE);
+    return groups < SEG_BWD_MAX_BLOCKS ? groups : SEG_BWD_MAX_BLOCKS;
+}
+template <int MAXV, bool DW>
+__global__ __launch_bounds__(256) void rmsnorm_seg_bwd_kernel(int M, int D, const bf16_t* x, int ldx, const bf16_t* w0,
+                                                              const bf16_t* w1, const float* rstd_in, const bf16_t* dy,
+                                                              int lddy, bf16_t* dx, int lddx, float* ws) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int seg = blockIdx.y, nseg = gridDim.y;
+    const bf16_t* w = seg ? w1 : w0;
+    const int nchunk = D >> 3;
+    float ww[MAXV][8], aw[DW ? MAXV : 1][8];
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nchunk) unpack8(*reinterpret_cast<const u32x4*>(w + c * 8), ww[i]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { if constexpr (DW) aw[i][e] = 0.f; if (c >= nchunk) ww[i][e] = 0.f; }
+    }
+    const int ngroups = (M + WAVES * ROWS_PER_WAVE - 1) / (WAVES * ROWS_PER_WAVE);
+    for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x)
+    for (int rr = 0; rr < ROWS_PER_WAVE; ++rr) {
+        const int64_t row = (int64_t)grp * (WAVES * ROWS_PER_WAVE) + wave * ROWS_PER_WAVE + rr;
+        if (row >= M) break;
+        float v[MAXV][8], g[MAXV][8];
+        load_row<MAXV>(x + row * ldx + (int64_t)seg * D, nchunk, lane, v);
+        load_row<MAXV>(dy + row * lddy + (int64_t)seg * D, nchunk, lane, g);
+        const float rstd = rstd_in[row * nseg + seg];
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float xn = v[i][e] * rstd;
+                if constexpr (DW) aw[i][e] = __builtin_fmaf(g[i][e], rbf(xn), aw[i][e]);
+                const float gg = rbf(g[i][e] * ww[i][e]);
+                v[i][e] = xn; g[i][e] = gg;
+                s = __builtin_fmaf(gg, xn, s);
+            }
+        s = wave_sum(s) / (float)D;
+        bf16_t* dr = dx + row * lddx + (int64_t)seg * D;
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nchunk) {
+                float o[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[e] = rstd * __builtin_fmaf(-v[i][e], s, g[i][e]);
+                *reinterpret_cast<u32x4*>(dr + c * 8) = pack8(o);
+            }
+        }
+    }
+    if constexpr (DW) {
+        __shared__ float red[(WAVES - 1) * MAXV * 512];
+        if (wave > 0) {
+#pragma unroll
+            for (int i = 0; i < MAXV; ++i)
+#pragma unroll
+                for (int e = 0; e < 8; e += 4)
+                    *reinterpret_cast<f32x4*>(red + ((wave - 1) * MAXV + i) * 512 + lane * 8 + e) =
+                        f32x4{aw[i][e], aw[i][e + 1], aw[i][e + 2], aw[i][e + 3]};
+        }
+        __syncthreads();
+        if (wave > 0) return;
+        float* wp = ws + ((int64_t)seg * gridDim.x + blockIdx.x) * D;
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nchunk) {
+#pragma unroll
+                for (int e = 0; e < 8; e += 4) {
+                    f32x4 t = f32x4{aw[i][e], aw[i][e + 1], aw[i][e + 2], aw[i][e + 3]};
+#pragma unroll
+                    for (int w2 = 0; w2 < WAVES - 1; ++w2)         // fixed order: wave 0 + wave 1 + wave 2 + wave 3
+                        t += *reinterpret_cast<const f32x4*>(red + (w2 * MAXV + i) * 512 + lane * 8 + e);
+                    *reinterpret_cast<f32x4*>(wp + c * 8 + e) = t;
+                }
+            }
+        }
+    }
+}
+
+// reduce_partials_bf16_kernel per segment: grid = (ceil(W / 64), nseg), segment s sums ws[s][G][W] into out0 / out1
+__global__ __launch_bounds__(256) void reduce_partials_seg_bf16_kernel(int G, int W, const float* ws, bf16_t* out0,
+                                                                       bf16_t* out1, int accumulate) {
+    const int j = blockIdx.x * 64 + (threadIdx.x & 63);
+    bf16_t* out = blockIdx.y ? out1 : out0;
+    float s = reduce_rows64(ws + (int64_t)blockIdx.y * G * W, G, W, j, j < W);
+    if (threadIdx.x >= 64 || j >= W) return;
+    if (accumulate) s = rbf(s) + bf2f(out[j]);
+    out[j] = f2bf(s);
+}
+
 // ------------------------------------------------------------------ strip kernels (512 columns x 32 rows per wave)
 constexpr int STRIP_ROWS = 32;            // rows per wave of the column sum
 constexpr int GATE_ROWS = 16;             // ... of the gate backward (three streams per row: twice the workgroups)
@@ -530,6 +674,60 @@ int yat_rmsnorm_bwd(int M, int D, const void* x, const void* w, const float* rst
     // rows past M never wrote their partial row: zero-filled? no -- every wave writes its (possibly zero) partials
     hipLaunchKernelGGL(reduce_partials_bf16_kernel, dim3((D + 63) / 64), dim3(256), 0, (hipStream_t)stream,
                        nblk * WAVES, D, (const float*)workspace, (bf16_t*)dw, accumulate_dw);
+    YAT_CHECK_LAUNCH();
+    return YAT_OK;
+}
+
+static bool seg_args_bad(int M, int D, int nseg, int ld) {
+    return M <= 0 || D <= 0 || (D & 7) || nseg < 1 || nseg > 2 || (ld & 7) || (int64_t)ld < (int64_t)nseg * D;
+}
+
+int yat_rmsnorm_seg_fwd(int M, int D, int nseg, float eps, const void* x, int ldx, const void* w0, const void* w1, void* y,
+                        int ldy, void* keep, float* rstd, yat_stream_t stream) {
+    if (seg_args_bad(M, D, nseg, ldx) || seg_args_bad(M, D, nseg, ldy) || !x || !w0 || (nseg == 2 && !w1) || !y || !rstd)
+        return YAT_EINVAL;
+    const int64_t tasks = (int64_t)M * nseg;
+    return dispatch_maxv(D, [&](auto mv) {
+        constexpr int MV = decltype(mv)::value;
+        hipLaunchKernelGGL((rmsnorm_seg_fwd_kernel<MV>), dim3((unsigned)((tasks + WAVES - 1) / WAVES)), dim3(256), 0,
+                           (hipStream_t)stream, M, D, nseg, eps, (const bf16_t*)x, ldx, (const bf16_t*)w0, (const bf16_t*)w1,
+                           (bf16_t*)y, ldy, (bf16_t*)keep, rstd);
+        YAT_CHECK_LAUNCH();
+        return YAT_OK;
+    });
+}
+
+uint64_t yat_rmsnorm_seg_bwd_workspace_bytes(int M, int D, int nseg) {
+    if (M <= 0 || D <= 0 || nseg < 1) return 0;
+    return (uint64_t)nseg * seg_bwd_blocks(M) * D * sizeof(float);              // one partial row per workgroup and segment
+}
+
+int yat_rmsnorm_seg_bwd(int M, int D, int nseg, const void* x, int ldx, const void* w0, const void* w1, const float* rstd,
+                        const void* dy, int lddy, void* dx, int lddx, void* dw0, void* dw1, int accumulate_dw,
+                        void* workspace, yat_stream_t stream) {
+    if (seg_args_bad(M, D, nseg, ldx) || seg_args_bad(M, D, nseg, lddy) || seg_args_bad(M, D, nseg, lddx) || !x || !w0 ||
+        (nseg == 2 && !w1) || !rstd || !dy || !dx)
+        return YAT_EINVAL;
+    const bool want_dw = dw0 != nullptr;                      // a frozen base under adapters passes no dw at all
+    if (nseg == 2 && want_dw != (dw1 != nullptr)) return YAT_EINVAL;
+    if (want_dw && !workspace) return YAT_EINVAL;
+    const int nblk = seg_bwd_blocks(M);
+    int rc = dispatch_maxv(D, [&](auto mv) {
+        constexpr int MV = decltype(mv)::value;
+        if (want_dw)
+            hipLaunchKernelGGL((rmsnorm_seg_bwd_kernel<MV, true>), dim3(nblk, nseg), dim3(256), 0, (hipStream_t)stream, M, D,
+                               (const bf16_t*)x, ldx, (const bf16_t*)w0, (const bf16_t*)w1, rstd, (const bf16_t*)dy, lddy,
+                               (bf16_t*)dx, lddx, (float*)workspace);
+        else
+            hipLaunchKernelGGL((rmsnorm_seg_bwd_kernel<MV, false>), dim3(nblk, nseg), dim3(256), 0, (hipStream_t)stream, M, D,
+                               (const bf16_t*)x, ldx, (const bf16_t*)w0, (const bf16_t*)w1, rstd, (const bf16_t*)dy, lddy,
+                               (bf16_t*)dx, lddx, (float*)nullptr);
+        YAT_CHECK_LAUNCH();
+        return YAT_OK;
+    });
+    if (rc || !want_dw) return rc;
+    hipLaunchKernelGGL(reduce_partials_seg_bf16_kernel, dim3((D + 63) / 64, nseg), dim3(256), 0, (hipStream_t)stream,
+                       nblk, D, (const float*)workspace, (bf16_t*)dw0, (bf16_t*)dw1, accumulate_dw);
     YAT_CHECK_LAUNCH();
     return YAT_OK;
 }

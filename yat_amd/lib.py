@@ -62,6 +62,9 @@ SIGNATURES = {
     "yat_rmsnorm_bwd_workspace_bytes": (U64, [I, I]),
     "yat_rmsnorm_fwd": (I, [I, I, F, P, P, P, P, P]),
     "yat_rmsnorm_bwd": (I, [I, I, P, P, P, P, P, P, I, P, P]),
+    "yat_rmsnorm_seg_bwd_workspace_bytes": (U64, [I, I, I]),
+    "yat_rmsnorm_seg_fwd": (I, [I, I, I, F, P, I, P, P, P, I, P, P, P]),
+    "yat_rmsnorm_seg_bwd": (I, [I, I, I, P, I, P, P, P, P, I, P, I, P, P, I, P, P]),
     "yat_linear_attn_workspace_bytes": (U64, [I, I, I]),
     "yat_linear_attn_fwd": (I, [I, I, I, P, I, I, I, P, I, P, P]),
     "yat_linear_attn_bwd": (I, [I, I, I, P, I, I, I, P, I, P, I, P, P, P]),

@@ -491,6 +491,51 @@ def rmsnorm_bwd(x2d, w, rstd, dy, dx, dw, workspace, accumulate_dw=False):
     _l.check(rc, "yat_rmsnorm_bwd")
 
 
+def _seg_view(t, D, nseg, name):
+    if t.dim() != 2 or t.shape[1] != nseg * D or t.stride(1) != 1:
+        raise ValueError(f"{name}: expected a [rows, {nseg * D}] view with unit column stride, got {tuple(t.shape)}")
+    return t.stride(0)
+
+
+def rmsnorm_seg_bwd_workspace_bytes(M, D, nseg):
+    return int(_lib().yat_rmsnorm_seg_bwd_workspace_bytes(M, D, nseg))
+
+
+def rmsnorm_seg_fwd(x, ws_, eps, y, rstd, keep=None):
+    """yat_rmsnorm_seg_fwd: RMSNorm of ``len(ws_)`` (1 | 2) adjacent D-wide segments per row.  ``x`` / ``y``: [M, nseg * D]
+    views of wider matrices (y may be x); ``keep``: contiguous [M, nseg * D] copy of the raw input; ``rstd``: fp32 [M, nseg]."""
+    nseg, D = len(ws_), ws_[0].shape[0]
+    M = x.shape[0]
+    _chk_bf16(x, y, keep, *ws_)
+    ldx, ldy = _seg_view(x, D, nseg, "rmsnorm_seg_fwd x"), _seg_view(y, D, nseg, "rmsnorm_seg_fwd y")
+    if keep is not None and (not keep.is_contiguous() or keep.numel() != M * nseg * D):
+        raise ValueError("rmsnorm_seg_fwd: keep must be a contiguous [M, nseg * D] buffer")
+    if rstd.dtype != torch.float32 or not rstd.is_contiguous() or rstd.numel() != M * nseg:
+        raise ValueError("rmsnorm_seg_fwd: rstd must be a contiguous fp32 [M, nseg] buffer")
+    rc = _lib().yat_rmsnorm_seg_fwd(M, D, nseg, eps, _p(x), ldx, _p(ws_[0]), _p(ws_[1]) if nseg > 1 else None, _p(y), ldy,
+                                    _p(keep), _p(rstd), _stream())
+    _dyn_rows(0, M)
+    _l.check(rc, "yat_rmsnorm_seg_fwd")
+    return y
+
+
+def rmsnorm_seg_bwd(x, ws_, rstd, dy, dx, dws=None, workspace=None, accumulate_dw=False):
+    """yat_rmsnorm_seg_bwd.  ``x``: the raw input ([M, nseg * D] view); ``dx`` may be ``dy``; ``dws`` None: dx only."""
+    nseg, D = len(ws_), ws_[0].shape[0]
+    M = x.shape[0]
+    _chk_bf16(x, dy, dx, *ws_, *(dws or ()))
+    ldx, lddy, lddx = (_seg_view(t, D, nseg, "rmsnorm_seg_bwd " + n) for t, n in ((x, "x"), (dy, "dy"), (dx, "dx")))
+    if dws is not None and len(dws) != nseg:
+        raise ValueError("rmsnorm_seg_bwd: one weight gradient per segment")
+    dw0 = None if dws is None else dws[0]
+    dw1 = None if dws is None or nseg < 2 else dws[1]
+    rc = _lib().yat_rmsnorm_seg_bwd(M, D, nseg, _p(x), ldx, _p(ws_[0]), _p(ws_[1]) if nseg > 1 else None, _p(rstd), _p(dy),
+                                    lddy, _p(dx), lddx, _p(dw0), _p(dw1), int(accumulate_dw), _p(workspace), _stream())
+    _dyn_rows(0, M)
+    _l.check(rc, "yat_rmsnorm_seg_bwd")
+    return dx
+
+
 def gate_bwd(dout, lin, gate, gate_ld, rows_per_batch, dlin, dgate_acc, acc_ld, workspace, dbias=None,
              accumulate_bias=False):
     """dlin = gate * dout, dgate += sum dout * lin; ``dbias`` (optional) (+)= column sum of dlin in the same pass."""

@@ -41,10 +41,14 @@ from .flat import FlatParamModule, schedule
 from .adapters import PendingWgrads, adapted_linear
 
 BF16 = torch.bfloat16
+QK_EPS = 1e-5          # [RECALL] diffusers Attention: norm_q / norm_k = RMSNorm(..., eps=1e-5) whatever the block's norm_eps
+
+
+QK_NORMS = (None, "rms_norm_across_heads")
 
 
 @dataclass
-class SanaConfig:
+class _SanaConfigFields:
     # defaults: utils/patched_sana_transformer.py:88-112 (SANA-1.6B)
     in_channels: int = 32
     out_channels: int = 32
@@ -83,6 +87,32 @@ class SanaConfig:
             raise ValueError("channel sizes must be multiples of 8 (16-byte vector accesses)")
         if self.cross_attention_head_dim > 128 or self.cross_attention_head_dim % 8:
             raise ValueError("cross attention head dim must be <= 128 and a multiple of 8")
+        if getattr(self, "qk_norm", None) not in QK_NORMS:
+            raise ValueError(f"qk_norm must be None or 'rms_norm_across_heads', got {self.qk_norm!r}")
+        if getattr(self, "qk_norm", None) is not None and D > 4096:
+            raise ValueError("qk_norm: the row kernels hold at most 4096 columns")
+
+
+class SanaConfig(_SanaConfigFields):
+    """The SANA-1.0 fields above plus ``qk_norm`` (SANA-1.5: "rms_norm_across_heads").  ``qk_norm`` is an ordinary keyword of
+    the constructor but deliberately not a dataclass field: callers build this config from a SANA-1.0 description by walking
+    ``SanaConfig.__dataclass_fields__``, and a description that predates the setting has no such attribute.  ``to_dict()`` is
+    ``asdict`` plus the setting."""
+
+    def __init__(self, *args, qk_norm: str | None = None, **kw):
+        super().__init__(*args, **kw)
+        self.qk_norm = qk_norm
+
+    def to_dict(self):
+        return {**asdict(self), "qk_norm": self.qk_norm}
+
+    def __eq__(self, other):
+        return isinstance(other, SanaConfig) and self.to_dict() == other.to_dict()
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "SanaConfig(" + ", ".join(f"{k}={v!r}" for k, v in self.to_dict().items()) + ")"
 
 
 def _param_specs(cfg: SanaConfig):
@@ -102,13 +132,20 @@ def _param_specs(cfg: SanaConfig):
     ]
     for i in range(cfg.num_layers):
         b = f"transformer_blocks.{i}."
+
+        def qkn(attn, b=b):
+            # SANA-1.5 ("qk_norm": "rms_norm_across_heads"): [RECALL] diffusers Attention.norm_q / norm_k = RMSNorm(D, eps=1e-5),
+            # weight only; behind the projections they follow.  Without the setting the list is SANA-1.0's.
+            return [(b + attn + ".norm_q.weight", (D,)), (b + attn + ".norm_k.weight", (D,))] if cfg.qk_norm else []
         specs += [
             (b + "scale_shift_table", (6, D)),
             (b + "attn1.to_q.weight", (D, D)), (b + "attn1.to_k.weight", (D, D)), (b + "attn1.to_v.weight", (D, D)),
+            *qkn("attn1"),
             (b + "attn1.to_out.0.weight", (D, D)), (b + "attn1.to_out.0.bias", (D,)),
             (b + "attn2.to_q.weight", (D, D)), (b + "attn2.to_q.bias", (D,)),
             (b + "attn2.to_k.weight", (D, D)), (b + "attn2.to_v.weight", (D, D)),
             (b + "attn2.to_k.bias", (D,)), (b + "attn2.to_v.bias", (D,)),
+            *qkn("attn2"),
             (b + "attn2.to_out.0.weight", (D, D)), (b + "attn2.to_out.0.bias", (D,)),
             (b + "ff.conv_inverted.weight", (2 * Hc, D, 1, 1)), (b + "ff.conv_inverted.bias", (2 * Hc,)),
             (b + "ff.conv_depth.weight", (2 * Hc, 1, 3, 3)), (b + "ff.conv_depth.bias", (2 * Hc,)),
@@ -140,7 +177,7 @@ class SanaTransformer2DModelHIP(FlatParamModule):
         cfg = cfg or SanaConfig(**cfg_kw)
         cfg.validate()
         self.cfg = cfg
-        self.config = SimpleNamespace(**asdict(cfg))          # diffusers-style `.config.sample_size`
+        self.config = SimpleNamespace(**cfg.to_dict())        # diffusers-style `.config.sample_size`
         specs = _param_specs(cfg)
         offs, total = self._alloc_flat(specs, device, bucket_first=lambda k: k.startswith("transformer_blocks.") and k.split(".", 2)[2] == "scale_shift_table")
         # bucket boundaries for data parallel reduction: head | one per block (+tail on the last)
@@ -158,7 +195,7 @@ class SanaTransformer2DModelHIP(FlatParamModule):
         g = torch.Generator(device=self.dev).manual_seed(seed)
         with torch.no_grad():
             for name, p in self.P.items():
-                if name == "caption_norm.weight":
+                if name == "caption_norm.weight" or name.endswith((".norm_q.weight", ".norm_k.weight")):
                     p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g, device=self.dev))
                 elif "scale_shift_table" in name:
                     p.copy_(torch.randn(p.shape, generator=g, device=self.dev) / p.shape[-1] ** 0.5)
@@ -225,6 +262,11 @@ class SanaTransformer2DModelHIP(FlatParamModule):
         S.kv2 = [tb(f"b{i}.kv2", 2 * D) for i in range(self.cfg.num_layers)]
         for A, kv in zip(S.blocks, S.kv2):
             A.kv2 = kv
+        if self.cfg.qk_norm:
+            S.k2_raw = [tb(f"b{i}.k2_raw", D) for i in range(self.cfg.num_layers)]
+            S.k2_rstd = [tb(f"b{i}.k2_rstd", 0, f32) for i in range(self.cfg.num_layers)]
+            for A, kr, ks in zip(S.blocks, S.k2_raw, S.k2_rstd):
+                A.k2_raw, A.k2_rstd = kr, ks
 
     def backward_device(self, dpred):
         S = self._saved
@@ -294,6 +336,7 @@ class SanaTransformer2DModelHIP(FlatParamModule):
         ad = self.adapters
         if ad is not None:
             ad.materialize(self.training)                     # this step's adapter state (yat_amd/adapters.py)
+        qkn = bool(cfg.qk_norm)
 
         def lin(x_, w_, bias_=None, out=None, **ep):
             """Linear of a (possibly adapted) target: with adapters, x delta_w^T is computed first and folded into the
@@ -321,7 +364,7 @@ class SanaTransformer2DModelHIP(FlatParamModule):
                                   out=tbuf("cap_c2", D))
             S.encn, S.enc_rstd = ops.rmsnorm_fwd(S.c2, P["caption_norm.weight"], 1e-5, tbuf("cap_n", D),
                                                  tbuf("cap_rstd", 0, torch.float32))
-            S.kv2, S.kv_ready = [], []
+            S.kv2, S.kv_ready, S.k2_raw, S.k2_rstd = [], [], [], []
             cur = torch.cuda.current_stream()
             for i in range(cfg.num_layers):
                 pre = f"transformer_blocks.{i}."
@@ -329,6 +372,14 @@ class SanaTransformer2DModelHIP(FlatParamModule):
                 wkv, _ = self._fused(pre + "attn2.to_k.weight", 2 * D, D)
                 bkv, _ = self._fused(pre + "attn2.to_k.bias", 2 * D)
                 S.kv2.append(lin(S.encn, wkv, bkv, out=tbuf(f"b{i}.kv2", 2 * D)))
+                if qkn:
+                    # attn2.norm_k on the text rows: the k columns of the fused k|v projection in place (biases included),
+                    # the raw k kept for the backward
+                    kcols = S.kv2[-1][:, :D]
+                    S.k2_raw.append(tbuf(f"b{i}.k2_raw", D))
+                    S.k2_rstd.append(tbuf(f"b{i}.k2_rstd", 0, torch.float32))
+                    ops.rmsnorm_seg_fwd(kcols, [P[pre + "attn2.norm_k.weight"]], QK_EPS, kcols, S.k2_rstd[-1],
+                                        keep=S.k2_raw[-1])
                 if side is not None:
                     S.kv_ready.append(self._ev_record(cur))
 
@@ -372,6 +423,11 @@ class SanaTransformer2DModelHIP(FlatParamModule):
             A.lse1 = buf(f"b{i}.lse1", (B, H1, N), f32) if A.softmax1 else None
             A.attn, A.lin1, A.x1, A.q2 = (buf(f"b{i}.{n}", (M, D)) for n in ("attn", "lin1", "x1", "q2"))
             A.kv2 = S.kv2[i]
+            if qkn:
+                # raw q|k of attn1 and raw q of attn2 (the projections are normalised in place), rstd per row and segment
+                A.qk1_raw, A.qk1_rstd = buf(f"b{i}.qk1_raw", (M, 2 * D)), buf(f"b{i}.qk1_rstd", (M, 2), f32)
+                A.q2_raw, A.q2_rstd = buf(f"b{i}.q2_raw", (M, D)), buf(f"b{i}.q2_rstd", (M,), f32)
+                A.k2_raw, A.k2_rstd = S.k2_raw[i], S.k2_rstd[i]
             A.o2, A.lse, A.x2 = buf(f"b{i}.o2", (M, D)), buf(f"b{i}.lse", (B, H2, N), f32), buf(f"b{i}.x2", (M, D))
             A.h2, A.mean2, A.rstd2 = buf(f"b{i}.h2", (M, D)), buf(f"b{i}.mean2", (M,), f32), buf(f"b{i}.rstd2", (M,), f32)
             A.z, A.s = buf(f"b{i}.z", (M, 2 * Hc)), buf(f"b{i}.s", (M, 2 * Hc))          # z: pre-activation, for SiLU'
@@ -400,6 +456,12 @@ class SanaTransformer2DModelHIP(FlatParamModule):
                                     A.rstd1[rs])
                 wqkv, _ = self._fused(pre + "attn1.to_q.weight", 3 * D, D)
                 lin(A.h1[rs], wqkv, out=A.qkv[rs])
+                if qkn:
+                    # q = norm_q(to_q(x)), k = norm_k(to_k(x)) before the head split and the ReLU / softmax scale: one
+                    # two-segment launch over the q|k columns, in place -- the attention kernels see normalised q and k
+                    qk_ = A.qkv[rs][:, :2 * D]
+                    ops.rmsnorm_seg_fwd(qk_, [P[pre + "attn1.norm_q.weight"], P[pre + "attn1.norm_k.weight"]], QK_EPS, qk_,
+                                        A.qk1_rstd[rs], keep=A.qk1_raw[rs])
                 if A.softmax1:
                     # AttnProcessor2_0 on attn1: plain softmax attention over the N tokens, 70 heads x 32, no mask --
                     # the cross-attention kernel with q, k, v = the three column blocks of the fused projection
@@ -413,6 +475,9 @@ class SanaTransformer2DModelHIP(FlatParamModule):
                                aux_out=A.lin1[rs], gate=mod2d[:, 2 * D:3 * D], ld_gate=6 * D, residual=xin,
                                rows_per_batch=N)
                 lin(A.x1[rs], P[pre + "attn2.to_q.weight"], P[pre + "attn2.to_q.bias"], out=A.q2[rs])
+                if qkn:
+                    ops.rmsnorm_seg_fwd(A.q2[rs], [P[pre + "attn2.norm_q.weight"]], QK_EPS, A.q2[rs], A.q2_rstd[rs],
+                                        keep=A.q2_raw[rs])
                 if side is not None:
                     self._ev_wait(stream, S.kv_ready[i])
                 kv = A.kv2 if packed else A.kv2[ts]          # packed: the whole matrix + this chain's row offsets
@@ -485,6 +550,12 @@ class SanaTransformer2DModelHIP(FlatParamModule):
         la_ws = buf("la_ws", (ops.linear_attn_workspace_bytes(B, N, H1),), u8)
         scale2 = 1.0 / math.sqrt(dh2)
         ad = self.adapters
+        qkn = bool(cfg.qk_norm)
+        # q/k norm backward: weight-gradient partial rows, one workspace per stream that runs it (the image rows on the
+        # dependent chain, the text rows behind dK/dV); a frozen base under adapters asks for dx only
+        qkn_dw = qkn and ad is None
+        ws_qkn = buf("ws_qkn", (ops.rmsnorm_seg_bwd_workspace_bytes(M, D, 2),), u8) if qkn_dw else None
+        ws_qkn_t = buf("ws_qkn_t", (ops.rmsnorm_seg_bwd_workspace_bytes(Mt_cap, D, 1),), u8) if qkn_dw else None
 
         def dgrad(dy_, w_, out=None, residual=None):
             """Input gradient through a (possibly adapted) target: dy W, plus dy delta_w accumulated in place."""
@@ -623,13 +694,16 @@ class SanaTransformer2DModelHIP(FlatParamModule):
             sd = (A.q2, A.kv2[:, :D], A.kv2[:, D:], B, N, T, H2, dh2, scale2, S.key_bias, S.kv_len, A.o2, do2, A.lse, delta,
                   dq2, dkv2[:, :D], dkv2[:, D:])
 
-            def dkv_part(parts, sd=sd, dkv2=dkv2):
+            def dkv_part(parts, sd=sd, dkv2=dkv2, A=A, pre=pre):
                 with text_scope():
                     if packed:
                         # the zero rows behind the last prompt (< 256 of them) belong to no image: dK/dV leaves them alone,
                         # the text-side GEMMs read them -- zero the last 256 rows first (the real ones among them are rewritten)
                         ops.zero_last_rows(dkv2, 256)
                     ops.sdpa_bwd(*sd, work=S.kv_work, parts=parts, kv_off=S.kv_off)
+                    if qkn:       # dK -> d(raw k) in place, before the text-side GEMMs read dkv2
+                        ops.rmsnorm_seg_bwd(A.k2_raw, [P[pre + "attn2.norm_k.weight"]], A.k2_rstd, dkv2[:, :D], dkv2[:, :D],
+                                            [G[pre + "attn2.norm_k.weight"]] if qkn_dw else None, ws_qkn_t, accumulate_dw=acc)
             # cross-attention backward: dQ (+delta) on the chain, dK/dV -- read only by the text-side gradients -- behind it
             if side is not None:
                 with text_scope():
@@ -637,6 +711,9 @@ class SanaTransformer2DModelHIP(FlatParamModule):
                 off_chain(lambda dkv_part=dkv_part: dkv_part(2))
             else:
                 dkv_part(3)
+            if qkn:               # dQ -> d(raw q) in place: the weight gradient and the input gradient below read dq2
+                ops.rmsnorm_seg_bwd(A.q2_raw, [P[pre + "attn2.norm_q.weight"]], A.q2_rstd, dq2, dq2,
+                                    [G[pre + "attn2.norm_q.weight"]] if qkn_dw else None, ws_qkn, accumulate_dw=acc)
             emit(dq2, A.x1, G[pre + "attn2.to_q.weight"], G[pre + "attn2.to_q.bias"], group=True)
             dx1 = dgrad(dq2, P[pre + "attn2.to_q.weight"], out=other, residual=dx2)    # dx1 = dx2 + dq2 Wq
             wkv, gkv = self._fused(pre + "attn2.to_k.weight", 2 * D, D)
@@ -662,6 +739,11 @@ class SanaTransformer2DModelHIP(FlatParamModule):
                              dqkv[:, D:2 * D], dqkv[:, 2 * D:])
             else:
                 ops.linear_attn_bwd(A.qkv, B, N, H1, D, 2 * D, dattn, dqkv, la_ws, state=A.la_state)
+            if qkn:               # the attention kernels' dq|dk are gradients of the normalised q|k: back through the norms
+                ops.rmsnorm_seg_bwd(A.qk1_raw, [P[pre + "attn1.norm_q.weight"], P[pre + "attn1.norm_k.weight"]], A.qk1_rstd,
+                                    dqkv[:, :2 * D], dqkv[:, :2 * D],
+                                    [G[pre + "attn1.norm_q.weight"], G[pre + "attn1.norm_k.weight"]] if qkn_dw else None,
+                                    ws_qkn, accumulate_dw=acc)
             wqkv, gqkv = self._fused(pre + "attn1.to_q.weight", 3 * D, D)
             emit(dqkv, A.h1, gqkv)
             dh1 = dgrad(dqkv, wqkv, out=buf(f"dh1.{par}", (M, D)))
@@ -750,6 +832,9 @@ class SanaTransformer2DModelHIP(FlatParamModule):
         cfgd.update({"_class_name": "SanaTransformer2DModel", "cross_attention_dim": self.cfg.cross_attention_dim,
                      "attention_bias": False, "dropout": 0.0, "norm_elementwise_affine": False,
                      "interpolation_scale": None})
+        if self.cfg.qk_norm:      # the keys a SANA-1.5 config.json carries
+            cfgd.update({"qk_norm": self.cfg.qk_norm, "guidance_embeds": False, "guidance_embeds_scale": 0.1,
+                         "timestep_scale": 1.0})
         with open(os.path.join(path, "config.json"), "w") as f:
             json.dump(cfgd, f, indent=2)
 
@@ -761,6 +846,15 @@ class SanaTransformer2DModelHIP(FlatParamModule):
         with open(os.path.join(path, "config.json")) as f:
             raw = json.load(f)
         known = {k: raw[k] for k in SanaConfig.__dataclass_fields__ if k in raw}
-        model = cls(SanaConfig(**known), device=device)
+        # SANA-1.5 keys: the q/k norm is built; guidance embeddings (SANA-Sprint) and a scaled timestep are not -- refuse them
+        # by name instead of training a different model (guidance_embeds_scale only matters with guidance_embeds: ignored)
+        if raw.get("guidance_embeds"):
+            raise ValueError("config.json: guidance_embeds = true (SANA-Sprint) is not supported")
+        if raw.get("timestep_scale") is not None and float(raw["timestep_scale"]) != 1.0:
+            raise ValueError(f"config.json: timestep_scale = {raw['timestep_scale']!r} is not supported (only 1.0)")
+        if raw.get("qk_norm") not in QK_NORMS:
+            raise ValueError(f"config.json: qk_norm = {raw['qk_norm']!r} is not supported "
+                             "(null or 'rms_norm_across_heads')")
+        model = cls(SanaConfig(**known, qk_norm=raw.get("qk_norm")), device=device)
         model.load_state_dict(load_file(os.path.join(path, "diffusion_pytorch_model.safetensors")))
         return model
