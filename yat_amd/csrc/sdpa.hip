@@ -21,73 +21,22 @@
 #include "common.hpp"
 #include "../../include/yat_hip.h"
 
-// Diagnostic build -DYAT_SDPA_STAMPS (scripts/sdpa_stamps.py): the waves of one workgroup sum, per loop segment, the s_memtime
-// ticks they spent there (backward kernels); the product build contains none of this.
-#ifdef YAT_SDPA_STAMPS
-__device__ unsigned int yat_sdpa_stamp_buf[8 * 16 + 8];
-// per workgroup: 100 MHz time at kernel entry, loop entry, loop exit, kernel exit; HW_ID; XCC_ID (wave 0 writes)
-__device__ unsigned int yat_sdpa_wg_times[4096 * 6];
-#define SD_WG_T(slot)                                                                                              \
-    do {                                                                                                            \
-        const unsigned wg_ = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);                        \
-        if (wg_ < 4096 && threadIdx.x == 0) {                                                                       \
-            yat_sdpa_wg_times[wg_ * 6 + slot] = (uint32_t)__builtin_amdgcn_s_memrealtime();                         \
-            if (slot == 0) {                                                                                        \
-                yat_sdpa_wg_times[wg_ * 6 + 4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);                         \
-                yat_sdpa_wg_times[wg_ * 6 + 5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);                        \
-            }                                                                                                       \
-        }                                                                                                           \
-    } while (0)
-#define SD_STAMP(slot)                                                  \
-    do {                                                                \
-        __builtin_amdgcn_sched_barrier(0);                              \
-        const uint32_t now_ = (uint32_t)__builtin_amdgcn_s_memtime();   \
-        st_sum[slot] += now_ - st_prev;                                 \
-        st_prev = now_;                                                 \
-        __builtin_amdgcn_sched_barrier(0);                              \
-    } while (0)
-#define SD_STAMP_BEGIN() uint32_t st_sum[16] = {}; uint32_t st_prev = (uint32_t)__builtin_amdgcn_s_memtime(); int st_n = 0; \
-    const uint32_t st_t0 = st_prev; const uint32_t st_r0 = (uint32_t)__builtin_amdgcn_s_memrealtime()
-#define SD_STAMP_END(cond)                                                                  \
-    do {                                                                                    \
-        if ((cond) && lane == 0) {                                                          \
-            for (int i_ = 0; i_ < 16; ++i_) yat_sdpa_stamp_buf[wave * 16 + i_] = st_sum[i_];  \
-            yat_sdpa_stamp_buf[128] = (unsigned)st_n;                                        \
-            if (wave == 0) { yat_sdpa_stamp_buf[129] = (uint32_t)__builtin_amdgcn_s_memtime() - st_t0;       \
-                             yat_sdpa_stamp_buf[130] = (uint32_t)__builtin_amdgcn_s_memrealtime() - st_r0; } \
-        }                                                                                   \
-    } while (0)
-#else
-#define SD_WG_T(slot) do {} while (0)
-#define SD_STAMP(slot) do {} while (0)
-#define SD_STAMP_BEGIN() do {} while (0)
-#define SD_STAMP_END(cond) do {} while (0)
-#endif
-
 // Wave priority by loop phase (s_setprio): raised while a wave issues its MFMA phases, dropped for its softmax.  Two workgroups
 // share a CU and their waves a SIMD at unrelated points of the same loop; with the priority the wave that has matrix work
 // gets the issue slots first and the partner's exponentials fill the gaps (and the s_setprio keeps the compiler from mixing
 // the phases).  Measured at N = T = 4096 (git history: scripts/gpu_attn_libs.sh; profiles/r04_l_*): dK/dV kernel 1.43 -> 1.36 ms (dh 72) and
-// 1.88 -> 1.80 ms (dh 64); forward 1.02 -> 0.98 ms at dh 64, level at dh 72; the dQ kernel 1 % slower with it -> not there.
+// 1.88 -> 1.80 ms (dh 64) -> there; forward 1.02 -> 0.98 ms at dh 64, level at dh 72 -> there; the dQ kernel 1 % slower with
+// it -> not there.
 // The opposite assignment (softmax high) costs the forward 3..7 %.
 // A tie-break between the two waves of a SIMD (matrix phases at level 2 or 3 by the parity of the wave slot, HW_ID bit 0, so that
 // waves reaching their MFMA phases together do not take turns) was measured in round 5 and is slower: forward 795 -> 827 us (dh 72),
 // 974 -> 1043 (dh 64), dK/dV 1360 -> 1397; the waves are not in step to begin with (profiles/r04_l_attention_phase_stamps.txt:
 // the partner wave adds 14 % to a wave's tile time).  profiles/r05_w_attention_priority_tiebreak.txt.
-#ifndef YAT_SDPA_PRIO_DKV
-#define YAT_SDPA_PRIO_DKV 1
-#endif
-#ifndef YAT_SDPA_PRIO_DQ
-#define YAT_SDPA_PRIO_DQ 0
-#endif
-#ifndef YAT_SDPA_PRIO_FWD
-#define YAT_SDPA_PRIO_FWD 1
-#endif
-#define SD_PRIO(on, level) do { if (on) __builtin_amdgcn_s_setprio(level); } while (0)
 
 namespace {
 
 constexpr int TILE = 16384;  // one [64][128] bf16 image
+constexpr int NW = 4;        // waves per workgroup, every kernel
 constexpr int DKV_STAGE = 2 * TILE + 512;   // one query-tile stage of the dK/dV kernel: Q, dO (one image each), lse, delta
 
 enum { IMG_ROW = 0, IMG_TR = 1 };
@@ -99,11 +48,10 @@ enum { IMG_ROW = 0, IMG_TR = 1 };
 // the rows left below the limit, so the hardware range check zero-fills the rows past it.  (The first version computed a
 // 64-bit row index, a compare and a select per piece and lane for every tile: ~55 vector instructions per 64-key tile in
 // loops that are bound by vector issue, not by the matrix pipe.)
-template <int NW = 4>
 struct TileSrc { uint32_t voff[16 / NW]; };
-template <int IMG, int NW = 4>
-__device__ __forceinline__ TileSrc<NW> tile_src(int ld, int dh, int wave, int lane) {
-    TileSrc<NW> t;
+template <int IMG>
+__device__ __forceinline__ TileSrc tile_src(int ld, int dh, int wave, int lane) {
+    TileSrc t;
 #pragma unroll
     for (int j = 0; j < 16 / NW; ++j) {
         const int piece = j * NW + wave;
@@ -121,8 +69,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const bf16_t* base, 
     const int64_t rows = row_limit - row0;
     return make_rsrc(base + row0 * ld + col0, rows > 0 ? (uint64_t)rows * ld * 2 : 0);
 }
-template <int NW = 4>
-__device__ __forceinline__ void stage_tile(__amdgpu_buffer_rsrc_t rsrc, char* lds, const TileSrc<NW>& src, int wave) {
+__device__ __forceinline__ void stage_tile(__amdgpu_buffer_rsrc_t rsrc, char* lds, const TileSrc& src, int wave) {
 #pragma unroll
     for (int j = 0; j < 16 / NW; ++j) lds_dma16(rsrc, (YAT_LDS void*)(lds + (j * NW + wave) * 1024), src.voff[j]);
 }
@@ -197,7 +144,8 @@ struct SdpaP {
     uint64_t stat_bytes;             // bytes of the lse / delta arrays (B*H*N*4)
     uint64_t bias_bytes;             // bytes of the key-bias array (B*T*4)
     const int* work; int n_work;     // dK/dV kernel: compact list of (batch, key tile) pairs, or null for the dense grid
-    int xcd_remap;                   // workgroup index -> (tile, head, image) so that an XCD owns contiguous (image, head) runs
+    int xcd_remap;                   // 1: workgroup index -> (tile, head, image) so that an XCD owns contiguous (image, head) runs
+                                     // (2: images fastest; the host never sets it, the kernels keep the arm: common_params)
     // Packed keys (yat_sdpa_*_packed): image b's K / V (and dK / dV) rows are [kv_off[b], kv_off[b] + kv_len[b]) of one
     // matrix without padding rows; key_bias / kv_len keep their [B, T] / [B] layout.  Null: rows [b T, b T + T).
     const int* kv_off;
@@ -258,11 +206,10 @@ __global__ __launch_bounds__(256) void sdpa_fwd_kernel(SdpaP p) {
     // long-sequence variant (self-attention over thousands of keys); QS = 1 keeps more workgroups for short key loops.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    SD_WG_T(0);
     const int g = lane >> 4, li = lane & 15;
     // the query blocks of one (image, head) read the same K / V: give them to one XCD (one L2) instead of all eight
     int bx, h, b;
-    if (p.xcd_remap == 2) xcd_contiguous3_zfast(bx, h, b);
+    if (p.xcd_remap == 2) xcd_contiguous3_zfast(bx, h, b);      // (never set: see common_params)
     else if (p.xcd_remap) xcd_contiguous3(bx, h, b);
     else { bx = blockIdx.x; h = blockIdx.y; b = blockIdx.z; }
     const int q0 = bx * (64 * QS) + wave * (16 * QS);
@@ -272,8 +219,8 @@ __global__ __launch_bounds__(256) void sdpa_fwd_kernel(SdpaP p) {
     const __amdgpu_buffer_rsrc_t rb = make_rsrc(p.bias, NOBIAS ? 0 : p.bias_bytes);
 
     const int64_t kvr0 = kv_row0(p, b), kvrl = kv_row_limit(p, kvr0, klim);
-    const TileSrc<> src_k = tile_src<IMG_ROW>(p.ldkv, p.dh, wave, lane);
-    TileSrc<> src_v = tile_src<IMG_TR>(p.ldkv, p.dh, wave, lane);
+    const TileSrc src_k = tile_src<IMG_ROW>(p.ldkv, p.dh, wave, lane);
+    TileSrc src_v = tile_src<IMG_TR>(p.ldkv, p.dh, wave, lane);
     if constexpr (ONES) {
         // column dh of the V image = 1.0 in every row of both stages, never touched by the DMA again
 #pragma unroll
@@ -327,21 +274,17 @@ __global__ __launch_bounds__(256) void sdpa_fwd_kernel(SdpaP p) {
     const float lazy = LAZY_LOG2 / ce;              // the threshold in the units of m
 
     int it = 0;
-    SD_WG_T(1);
-    SD_STAMP_BEGIN();
     for (int k0 = 0; k0 < klim; k0 += 64, ++it) {
         char* cur = smem + (it & 1) * FWD_STAGE;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                                       // tile `it` landed for every wave; stage (it+1)&1 is free
-        SD_STAMP(0);
         if (k0 + 64 < klim) stage(k0 + 64, smem + ((it + 1) & 1) * FWD_STAGE);
-        SD_STAMP(1);
         if constexpr (!NOBIAS) mask_tail_bias(cur + 2 * TILE, k0, p.T, wave, lane);
         const char* Ks = cur;
         const char* Vs = cur + TILE;
         const float* bias_s = reinterpret_cast<const float*>(cur + 2 * TILE);
 
-        SD_PRIO(YAT_SDPA_PRIO_FWD, 1);
+        __builtin_amdgcn_s_setprio(1);
         f32x4 s[QS][4];
 #pragma unroll
         for (int nj = 0; nj < 4; ++nj) {
@@ -374,8 +317,7 @@ __global__ __launch_bounds__(256) void sdpa_fwd_kernel(SdpaP p) {
                     for (int r = 0; r < 4; ++r) s[qs][nj][r] = __builtin_fmaf(s[qs][nj][r], p.scale, bv[r]);
             }
         }
-        SD_STAMP(2);
-        SD_PRIO(YAT_SDPA_PRIO_FWD, 0);
+        __builtin_amdgcn_s_setprio(0);
         // tile maxima; does any row of this wave outrun its reference by more than the threshold?
         float mx[QS];
         bool grow = false;
@@ -419,8 +361,7 @@ __global__ __launch_bounds__(256) void sdpa_fwd_kernel(SdpaP p) {
             pf0[qs] = acc_to_frag(s[qs][0], s[qs][1]);
             pf1[qs] = acc_to_frag(s[qs][2], s[qs][3]);
         }
-        SD_STAMP(3);
-        SD_PRIO(YAT_SDPA_PRIO_FWD, 1);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
             const bf16x8 v0 = frag_tr_acc(Vs, 0, dt * 16, lane), v1 = frag_tr_acc(Vs, 32, dt * 16, lane);
@@ -430,13 +371,7 @@ __global__ __launch_bounds__(256) void sdpa_fwd_kernel(SdpaP p) {
                 o[qs][dt] = mfma16(v1, pf1[qs], o[qs][dt]);
             }
         }
-        SD_STAMP(4);
-#ifdef YAT_SDPA_STAMPS
-        ++st_n;
-#endif
     }
-    SD_STAMP_END(bx == 3 && h == 1 && b == 0);
-    SD_WG_T(2);
 #pragma unroll
     for (int qs = 0; qs < QS; ++qs) {
         if constexpr (ONES) {
@@ -461,7 +396,6 @@ __global__ __launch_bounds__(256) void sdpa_fwd_kernel(SdpaP p) {
             if (g == 0 && p.lse) p.lse[((int64_t)b * p.H + h) * p.N + qi] = m[qs] * (NOBIAS ? p.scale : 1.0f) + __logf(l[qs]);
         }
     }
-    SD_WG_T(3);
 }
 
 // (A software-pipelined forward for the long no-bias key loops -- the Q K^T product of tile t+1 issued beside the exponentials
@@ -473,16 +407,16 @@ __global__ __launch_bounds__(256) void sdpa_fwd_kernel(SdpaP p) {
 // Stage = K (TR-swizzled image: read row-wise for S = Q K^T and transposed for dQ = dS K), V (ROW image), key bias.
 // Two stages, one barrier per key tile, as in the forward.
 constexpr int DQ_STAGE = 2 * TILE + 256;
-template <int KS, int DT, int QS, bool NOBIAS, int NW = 4>
+template <int KS, int DT, int QS, bool NOBIAS>
 __global__ __launch_bounds__(64 * NW) void sdpa_bwd_dq_kernel(SdpaP p) {
-    // NW waves: the workgroup covers 16 * NW * QS queries and shares each key tile's LDS-DMA among them
+    // the workgroup covers 16 * NW * QS queries and shares each key tile's LDS-DMA among its waves
     // NOBIAS (no key bias, every key attends): P = exp2(s * (scale log2e) - lse log2e) in one FMA + exp, no bias tile.  Keys
     // past T in the last tile need no mask here: their K rows are zero-filled, so whatever dS they get multiplies zeros.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, li = lane & 15;
     int bx, h, b;
-    if (p.xcd_remap == 2) xcd_contiguous3_zfast(bx, h, b);
+    if (p.xcd_remap == 2) xcd_contiguous3_zfast(bx, h, b);      // (never set: see common_params)
     else if (p.xcd_remap) xcd_contiguous3(bx, h, b);
     else { bx = blockIdx.x; h = blockIdx.y; b = blockIdx.z; }
     const int q0 = bx * (16 * NW * QS) + wave * (16 * QS);               // QS 16-query sub-tiles per wave, as in the forward
@@ -494,10 +428,10 @@ __global__ __launch_bounds__(64 * NW) void sdpa_bwd_dq_kernel(SdpaP p) {
     const float ce = p.scale * LOG2E;
 
     const int64_t kvr0 = kv_row0(p, b), kvrl = kv_row_limit(p, kvr0, klim);
-    const TileSrc<NW> src_k = tile_src<IMG_TR, NW>(p.ldkv, p.dh, wave, lane), src_v = tile_src<IMG_ROW, NW>(p.ldkv, p.dh, wave, lane);
+    const TileSrc src_k = tile_src<IMG_TR>(p.ldkv, p.dh, wave, lane), src_v = tile_src<IMG_ROW>(p.ldkv, p.dh, wave, lane);
     auto stage = [&](int k0, char* base) {
-        stage_tile<NW>(tile_rsrc(p.k, kvr0 + k0, kvrl, p.ldkv, col0), base, src_k, wave);
-        stage_tile<NW>(tile_rsrc(p.v, kvr0 + k0, kvrl, p.ldkv, col0), base + TILE, src_v, wave);
+        stage_tile(tile_rsrc(p.k, kvr0 + k0, kvrl, p.ldkv, col0), base, src_k, wave);
+        stage_tile(tile_rsrc(p.v, kvr0 + k0, kvrl, p.ldkv, col0), base + TILE, src_v, wave);
         if (!NOBIAS && wave == 0) {
             const int key = k0 + lane;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (YAT_LDS void*)(base + 2 * TILE), 4,
@@ -532,15 +466,11 @@ __global__ __launch_bounds__(64 * NW) void sdpa_bwd_dq_kernel(SdpaP p) {
     }
 
     int it = 0;
-    SD_STAMP_BEGIN();
     for (int k0 = 0; k0 < klim; k0 += 64, ++it) {
         char* cur = smem + (it & 1) * DQ_STAGE;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        SD_STAMP(0);
         if (k0 + 64 < klim) stage(k0 + 64, smem + ((it + 1) & 1) * DQ_STAGE);
-        SD_STAMP(1);
-        SD_PRIO(YAT_SDPA_PRIO_DQ, 1);
         if constexpr (!NOBIAS) mask_tail_bias(cur + 2 * TILE, k0, p.T, wave, lane);
         const char* Kt = cur;
         const char* Vs = cur + TILE;
@@ -564,8 +494,6 @@ __global__ __launch_bounds__(64 * NW) void sdpa_bwd_dq_kernel(SdpaP p) {
                 }
             }
         }
-        SD_STAMP(2);
-        SD_PRIO(YAT_SDPA_PRIO_DQ, 0);
         bf16x8 f0[QS], f1[QS];
 #pragma unroll
         for (int qs = 0; qs < QS; ++qs) {
@@ -583,8 +511,6 @@ __global__ __launch_bounds__(64 * NW) void sdpa_bwd_dq_kernel(SdpaP p) {
             f0[qs] = acc_to_frag(s[qs][0], s[qs][1]);
             f1[qs] = acc_to_frag(s[qs][2], s[qs][3]);
         }
-        SD_STAMP(3);
-        SD_PRIO(YAT_SDPA_PRIO_DQ, 1);
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
             const bf16x8 k0f = frag_tr_acc(Kt, 0, dt * 16, lane), k1f = frag_tr_acc(Kt, 32, dt * 16, lane);
@@ -594,13 +520,7 @@ __global__ __launch_bounds__(64 * NW) void sdpa_bwd_dq_kernel(SdpaP p) {
                 acc[qs][dt] = mfma16(k1f, f1[qs], acc[qs][dt]);
             }
         }
-        SD_STAMP(4);
-        SD_PRIO(YAT_SDPA_PRIO_DQ, 0);
-#ifdef YAT_SDPA_STAMPS
-        ++st_n;
-#endif
     }
-    SD_STAMP_END(bx == 3 && h == 1 && b == 0);
 #pragma unroll
     for (int qs = 0; qs < QS; ++qs) {
         const int qi = q0 + qs * 16 + li;
@@ -625,16 +545,15 @@ __device__ __forceinline__ f32x4 score_start(const float* lse_s, int q, float in
 }
 // (two waves per SIMD asked for where the kernel fits them -- head dims up to 96; the allocator otherwise lands the dh-72 dense
 //  instantiation at 260 registers, one wave per SIMD: 1.41 -> 1.96 ms when that happened in round 3)
-template <int KS, int DT, int KB, int NW, bool NOBIAS>
-__global__ __launch_bounds__(64 * NW, (KS <= 3 && NW == 4) ? 2 : 1) void sdpa_bwd_dkv_kernel(SdpaP p) {
+template <int KS, int DT, int KB, bool NOBIAS>
+__global__ __launch_bounds__(64 * NW, KS <= 3 ? 2 : 1) void sdpa_bwd_dkv_kernel(SdpaP p) {
     // NOBIAS: as in the dQ kernel (the scale folded into the exp's FMA); keys past T need no mask -- their dK / dV rows are
     // not stored and no other key's result depends on them.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // stage layout: Q | dO (TR-swizzled images, read row-wise for S / dP and transposed for dK / dV) | lse[64] | delta[64]
     // (staging a ROW and a TR image of each, as before, made the loop LDS-DMA bound: 64 KB per query tile per CU)
-    // KB = 16-key sub-tiles per wave, NW = waves: the workgroup owns KT = 16*KB*NW keys.  NW = 8 is the long-sequence
-    // variant (dense grid only): every Q / dO tile staged in LDS serves 128 keys, so the per-wave LDS-DMA issue cost (the
-    // bound of this loop at NW = 4: ~18 issues per 44 MFMAs) halves while the per-wave register footprint stays put.
+    // KB = 16-key sub-tiles per wave: the workgroup owns KT = 16*KB*NW keys.  (Eight waves of 16 keys, which halve the per-wave
+    // LDS-DMA issue cost of a 128-key workgroup instead, were measured slower than KB = 2: 1.97 vs 1.80 ms at N = T = 4096.)
     constexpr int KT = 16 * KB * NW;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, li = lane & 15;
@@ -645,8 +564,8 @@ __global__ __launch_bounds__(64 * NW, (KS <= 3 && NW == 4) ? 2 : 1) void sdpa_bw
     // key tiles of one (image, head) share Q / dO in one L2.  With the compact work list (grid = (work items, heads)) every
     // unit is ONE key tile -- equal work -- so contiguous runs are balanced whatever the lengths; units x fastest = the key
     // tiles of one image, one head, side by side (round 6: the list path ran unmapped, the three tiles of an (image, head)
-    // on three XCDs, each fetching its own copy of Q and dO).  Dense grid: mode 2 = images fastest among the pairs (ragged).
-    if (p.xcd_remap == 2 && !p.work) xcd_contiguous3_zfast(bx, h, bz);
+    // on three XCDs, each fetching its own copy of Q and dO).
+    if (p.xcd_remap == 2 && !p.work) xcd_contiguous3_zfast(bx, h, bz);      // (never set: see common_params)
     else if (p.xcd_remap) xcd_contiguous3(bx, h, bz);
     const int b = p.work ? p.work[2 * bx] : bz;
     const int tile = p.work ? p.work[2 * bx + 1] : bx;
@@ -678,7 +597,7 @@ __global__ __launch_bounds__(64 * NW, (KS <= 3 && NW == 4) ? 2 : 1) void sdpa_bw
             }
         }
     }
-    const TileSrc<NW> src_q = tile_src<IMG_TR, NW>(p.ldq, p.dh, wave, lane), src_do = tile_src<IMG_TR, NW>(p.lddo, p.dh, wave, lane);
+    const TileSrc src_q = tile_src<IMG_TR>(p.ldq, p.dh, wave, lane), src_do = tile_src<IMG_TR>(p.lddo, p.dh, wave, lane);
     const uint64_t stat_bytes = p.stat_bytes;
     const __amdgpu_buffer_rsrc_t rlse = make_rsrc(p.lse, stat_bytes), rdel = make_rsrc(p.delta, stat_bytes);
     const int64_t kvr0 = kv_row0(p, b), klimrow = kv_row_limit(p, kvr0, klim);
@@ -716,8 +635,8 @@ __global__ __launch_bounds__(64 * NW, (KS <= 3 && NW == 4) ? 2 : 1) void sdpa_bw
     // double-buffered query tiles: tile qt+1 is DMA'd while tile qt is consumed
     auto stage_q = [&](int q0, char* base) {
         const int64_t r0 = (int64_t)b * p.N + q0, rl = (int64_t)b * p.N + p.N;
-        stage_tile<NW>(tile_rsrc(p.q, r0, rl, p.ldq, col0), base, src_q, wave);
-        stage_tile<NW>(tile_rsrc(p.dout, r0, rl, p.lddo, col0), base + TILE, src_do, wave);
+        stage_tile(tile_rsrc(p.q, r0, rl, p.ldq, col0), base, src_q, wave);
+        stage_tile(tile_rsrc(p.dout, r0, rl, p.lddo, col0), base + TILE, src_do, wave);
         // lse / delta rows by 4-byte LDS-DMA as well: an ordinary VGPR load here would make the compiler wait
         // vmcnt(0) for it -- draining the 16 tile DMAs just issued and undoing the double buffering.  Rows past N read
         // as 0 (range check); their Q and dO rows are zero too, so P stays finite and dS = P * (0 - 0) = 0.
@@ -730,15 +649,12 @@ __global__ __launch_bounds__(64 * NW, (KS <= 3 && NW == 4) ? 2 : 1) void sdpa_bw
         }
     };
     stage_q(0, smem);
-    SD_STAMP_BEGIN();
     for (int q0 = 0, it = 0; q0 < p.N; q0 += 64, ++it) {
         char* cur = smem + (it & 1) * DKV_STAGE;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();      // tile `it` landed everywhere; every wave is done with the other stage
-        SD_STAMP(0);
         if (q0 + 64 < p.N) stage_q(q0 + 64, smem + ((it + 1) & 1) * DKV_STAGE);
-        SD_STAMP(1);
-        SD_PRIO(YAT_SDPA_PRIO_DKV, 1);
+        __builtin_amdgcn_s_setprio(1);
         const char* Qt = cur;
         const char* Ot = cur + TILE;
         const float* lse_s = reinterpret_cast<const float*>(cur + 2 * TILE);
@@ -819,8 +735,7 @@ __global__ __launch_bounds__(64 * NW, (KS <= 3 && NW == 4) ? 2 : 1) void sdpa_bw
                         }
                     }
                 }
-                SD_STAMP(2 + 3 * half);
-                SD_PRIO(YAT_SDPA_PRIO_DKV, 0);
+                __builtin_amdgcn_s_setprio(0);
                 bf16x8 pf[KB], sf[KB];
 #pragma unroll
                 for (int kb = 0; kb < KB; ++kb) {
@@ -836,8 +751,7 @@ __global__ __launch_bounds__(64 * NW, (KS <= 3 && NW == 4) ? 2 : 1) void sdpa_bw
                     pf[kb] = acc_to_frag(s[kb][0], s[kb][1]);
                     sf[kb] = acc_to_frag(dp[kb][0], dp[kb][1]);
                 }
-                SD_STAMP(3 + 3 * half);
-                SD_PRIO(YAT_SDPA_PRIO_DKV, 1);
+                __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt) {
                     const bf16x8 of = frag_tr_acc(Ot, 32 * half, dt * 16, lane), qf_ = frag_tr_acc(Qt, 32 * half, dt * 16, lane);
@@ -847,14 +761,9 @@ __global__ __launch_bounds__(64 * NW, (KS <= 3 && NW == 4) ? 2 : 1) void sdpa_bw
                         adk[kb][dt] = mfma16(qf_, sf[kb], adk[kb][dt]);
                     }
                 }
-                SD_STAMP(4 + 3 * half);
             }
         }
-#ifdef YAT_SDPA_STAMPS
-        ++st_n;
-#endif
     }
-    SD_STAMP_END(tile == 3 && h == 1 && b == 0);
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
         if (!kvalid[kb]) continue;
@@ -874,28 +783,27 @@ __global__ __launch_bounds__(64 * NW, (KS <= 3 && NW == 4) ? 2 : 1) void sdpa_bw
     }
 }
 
-#ifdef YAT_SDPA_ONE_WG            // diagnostic: LDS padded so that one workgroup fits a CU (a wave alone on its SIMD)
-constexpr int FWD_LDS = 100 * 1024, DQ_LDS = 100 * 1024, DKV_LDS = 100 * 1024;
-#else
 constexpr int FWD_LDS = 2 * FWD_STAGE, DQ_LDS = 2 * DQ_STAGE, DKV_LDS = 2 * DKV_STAGE;
-#endif
+
+// every launch of this file: the kernel's dynamic-LDS limit is raised once per instantiation, NW waves per workgroup
+template <void (*KERNEL)(SdpaP), int LDS>
+int launch(const SdpaP& p, dim3 grid, hipStream_t stream) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        if (hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return YAT_EINVAL;
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(KERNEL, grid, dim3(64 * NW), LDS, stream, p);
+    YAT_CHECK_LAUNCH();
+    return YAT_OK;
+}
 
 // The LDS images stay 128 columns wide (columns past dh are zero-filled by the DMA range check); what the head dim decides
 // is how many of the 32-wide k-steps (KS) and 16-wide output tiles (DT) carry data.  Instantiations: dh <= 32 (SANA's
 // softmax variant of attn1), <= 64, <= 80 (PixArt-Sigma: 72), <= 112 (SANA cross-attention), <= 128.
 template <int KS, int DT, int QS, bool NOBIAS, bool ONES>
 int launch_fwd_qs(const SdpaP& p, int B, hipStream_t stream) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)sdpa_fwd_kernel<KS, DT, QS, NOBIAS, ONES>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                FWD_LDS) != hipSuccess)
-            return YAT_EINVAL;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((sdpa_fwd_kernel<KS, DT, QS, NOBIAS, ONES>), dim3((p.N + 64 * QS - 1) / (64 * QS), p.H, B), dim3(256),
-                       FWD_LDS, stream, p);
-    YAT_CHECK_LAUNCH();
-    return YAT_OK;
+    return launch<sdpa_fwd_kernel<KS, DT, QS, NOBIAS, ONES>, FWD_LDS>(p, dim3((p.N + 64 * QS - 1) / (64 * QS), p.H, B), stream);
 }
 template <int KS, int DT, bool NOBIAS, bool ONES>
 int launch_fwd_x(const SdpaP& p, int B, int wide, hipStream_t stream) {
@@ -927,23 +835,11 @@ int launch_fwd_nobias(const SdpaP& p, int B, int wide, hipStream_t stream) {
     // (dh 104 would need <4, 7>: its ones column sits in output tile 6, not 7 -- not a head dim of any model here)
     return -100;            // no ONES instantiation: the caller falls back to the head-dim classes
 }
-#ifndef YAT_SDPA_DQ_NW
-#define YAT_SDPA_DQ_NW 4
-#endif
 template <int KS, int DT, int QS>
 int launch_dq_qs(const SdpaP& p, int B, hipStream_t stream) {
-    constexpr int NW = QS >= 2 ? YAT_SDPA_DQ_NW : 4;
-    const void* fn = p.bias ? (const void*)sdpa_bwd_dq_kernel<KS, DT, QS, false, NW> : (const void*)sdpa_bwd_dq_kernel<KS, DT, QS, true, NW>;
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[p.bias ? 0 : 1]) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, DQ_LDS) != hipSuccess) return YAT_EINVAL;
-        attr_set[p.bias ? 0 : 1] = true;
-    }
     const dim3 grid((p.N + 16 * NW * QS - 1) / (16 * NW * QS), p.H, B);
-    if (p.bias) hipLaunchKernelGGL((sdpa_bwd_dq_kernel<KS, DT, QS, false, NW>), grid, dim3(64 * NW), DQ_LDS, stream, p);
-    else hipLaunchKernelGGL((sdpa_bwd_dq_kernel<KS, DT, QS, true, NW>), grid, dim3(64 * NW), DQ_LDS, stream, p);
-    YAT_CHECK_LAUNCH();
-    return YAT_OK;
+    return p.bias ? launch<sdpa_bwd_dq_kernel<KS, DT, QS, false>, DQ_LDS>(p, grid, stream)
+                  : launch<sdpa_bwd_dq_kernel<KS, DT, QS, true>, DQ_LDS>(p, grid, stream);
 }
 template <int KS, int DT>
 int launch_dq(const SdpaP& p, int B, int wide, hipStream_t stream) {
@@ -952,27 +848,21 @@ int launch_dq(const SdpaP& p, int B, int wide, hipStream_t stream) {
     }
     return wide ? launch_dq_qs<KS, DT, 2>(p, B, stream) : launch_dq_qs<KS, DT, 1>(p, B, stream);
 }
-template <int KS, int DT, int KB, int NW>
+template <int KS, int DT, int KB>
 int launch_dkv_kb(const SdpaP& p, int B, hipStream_t stream) {
-    const void* fn = p.bias ? (const void*)sdpa_bwd_dkv_kernel<KS, DT, KB, NW, false> : (const void*)sdpa_bwd_dkv_kernel<KS, DT, KB, NW, true>;
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[p.bias ? 0 : 1]) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS) != hipSuccess) return YAT_EINVAL;
-        attr_set[p.bias ? 0 : 1] = true;
-    }
     constexpr int KT = 16 * KB * NW;
     const dim3 grid = p.work ? dim3(p.n_work, p.H, 1) : dim3((p.T + KT - 1) / KT, p.H, B);
-    if (p.bias) hipLaunchKernelGGL((sdpa_bwd_dkv_kernel<KS, DT, KB, NW, false>), grid, dim3(64 * NW), DKV_LDS, stream, p);
-    else hipLaunchKernelGGL((sdpa_bwd_dkv_kernel<KS, DT, KB, NW, true>), grid, dim3(64 * NW), DKV_LDS, stream, p);
-    YAT_CHECK_LAUNCH();
-    return YAT_OK;
+    return p.bias ? launch<sdpa_bwd_dkv_kernel<KS, DT, KB, false>, DKV_LDS>(p, grid, stream)
+                  : launch<sdpa_bwd_dkv_kernel<KS, DT, KB, true>, DKV_LDS>(p, grid, stream);
 }
 template <int KS, int DT>
-int launch_dkv(const SdpaP& p, int B, int wide, hipStream_t stream) {
-    if (wide == 2) return launch_dkv_kb<KS, DT, 2, 4>(p, B, stream);      // 32 keys per wave: measured slower, see below
-    return wide ? launch_dkv_kb<KS, DT, 1, 8>(p, B, stream) : launch_dkv_kb<KS, DT, 1, 4>(p, B, stream);
+int launch_dkv(const SdpaP& p, int B, bool wide, hipStream_t stream) {
+    if constexpr (KS <= 3) {
+        if (wide) return launch_dkv_kb<KS, DT, 2>(p, B, stream);          // 128-key workgroups, 32 keys per wave (dh <= 80)
+    }
+    return launch_dkv_kb<KS, DT, 1>(p, B, stream);
 }
-#define YAT_SDPA_DISPATCH(fn, dh, ...)                      \
+#define SDPA_DISPATCH(fn, dh, ...)                          \
     ((dh) <= 32    ? fn<1, 2>(__VA_ARGS__)                  \
      : (dh) <= 64  ? fn<2, 4>(__VA_ARGS__)                  \
      : (dh) <= 80  ? fn<3, 5>(__VA_ARGS__)                  \
@@ -987,39 +877,48 @@ int check_common(int B, int N, int T, int H, int dh, int ldq, int ldkv, int64_t 
     return YAT_OK;
 }
 
+// the fields the forward and the backward share
+SdpaP common_params(int B, int N, int T, int H, int dh, float scale, const void* q, int ldq, const void* k, const void* v, int ldkv,
+                    const int* kv_off, int64_t kv_rows, const float* key_bias, const int* kv_len, const void* out, int ldo,
+                    const float* lse) {
+    SdpaP p{};
+    p.N = N; p.T = T; p.H = H; p.dh = dh; p.scale = scale;
+    p.q = (const bf16_t*)q; p.ldq = ldq; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.ldkv = ldkv;
+    p.bias = key_bias; p.kv_len = kv_len; p.out = (bf16_t*)out; p.ldo = ldo; p.lse = (float*)lse; p.kv_off = kv_off;
+    p.q_bytes = (uint64_t)B * N * ldq * 2; p.kv_bytes = (uint64_t)kv_rows * ldkv * 2; p.bias_bytes = (uint64_t)B * T * 4;
+    // XCD-contiguous order only for long uniform key loops (self-attention): with ragged kv_len the images with long
+    // captions would pile up on one XCD (measured: T = 300 cross-attention 81 -> 104 us; N = T = 4096 1175 -> 1117 us).
+    // (Round 6: a second order -- pairs ordered images-fastest, so that an XCD's run holds whole (image, head) pairs, one L2
+    // copy of their K / V instead of eight, and every image about equally often -- measured on the SANA cross-attention, B = 8,
+    // ragged 20..300 keys: forward 44.9 -> 46.0 us, dQ 59.0 -> 63.9 us: the K / V copies were never what these kernels wait
+    // for: profiles/r06_b_cross_attention_xcd_order.txt.  No switch reaches it any more.  The kernels keep its never-taken
+    // `xcd_remap == 2` arm all the same: without it the dh-64 no-bias dK/dV kernel measured 0.9 % slower (scalar registers
+    // assigned differently through its loop), profiles/sdpa_shipped_a_bench.txt.)
+    p.xcd_remap = T >= 1024;
+    return p;
+}
+
 int sdpa_fwd_impl(int B, int N, int T, int H, int dh, float scale, const void* q, int ldq, const void* k, const void* v,
                   int ldkv, const int* kv_off, int64_t kv_rows, const float* key_bias, const int* kv_len, void* out, int ldo,
                   float* lse, yat_stream_t stream) {
     if (check_common(B, N, T, H, dh, ldq, ldkv, kv_rows) || (ldo & 3) || !q || !k || !v || !out) return YAT_EINVAL;
     if (kv_off && !kv_len) return YAT_EINVAL;          // packed keys: every image says how many rows it owns (all >= 1)
     if (!key_bias && (kv_len || kv_off)) return YAT_EINVAL;      // no bias = plain attention over all T keys of every image
-    SdpaP p{};
-    p.N = N; p.T = T; p.H = H; p.dh = dh; p.scale = scale;
-    p.q = (const bf16_t*)q; p.ldq = ldq; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.ldkv = ldkv;
-    p.bias = key_bias; p.kv_len = kv_len; p.out = (bf16_t*)out; p.ldo = ldo; p.lse = lse; p.kv_off = kv_off;
-    p.q_bytes = (uint64_t)B * N * ldq * 2; p.kv_bytes = (uint64_t)kv_rows * ldkv * 2; p.bias_bytes = (uint64_t)B * T * 4;
-    // XCD-contiguous order only for long uniform key loops (self-attention): with ragged kv_len the images with long
-    // captions would pile up on one XCD (measured: T = 300 cross-attention 81 -> 104 us; N = T = 4096 1175 -> 1117 us)
-    // (round 6: mode 2 -- pairs ordered images-fastest, so that an XCD's run holds whole (image, head) pairs, one L2 copy of
-    // their K / V instead of eight, and every image about equally often -- measured on the SANA cross-attention, B = 8, ragged
-    // 20..300 keys: forward 44.9 -> 46.0 us, dQ 59.0 -> 63.9 us: the K / V copies were never what these kernels wait for.
-    // Not the default; reachable in tuning builds, YAT_SDPA_XCD=2.  profiles/r06_b_cross_attention_xcd_order.txt)
-    static const int xcd_env = YAT_TUNE_INT("YAT_SDPA_XCD", -1);
-    p.xcd_remap = xcd_env >= 0 ? xcd_env : (T >= 1024);
+    const SdpaP p = common_params(B, N, T, H, dh, scale, q, ldq, k, v, ldkv, kv_off, kv_rows, key_bias, kv_len, out, ldo, lse);
     // 128-query workgroups once there are enough of them to fill the chip twice over (PixArt-Sigma: N = 4096)
     static const int wide_env = YAT_TUNE_INT("YAT_SDPA_WIDE", -1);
     // ... and 192-query ones (three sub-tiles per wave: K / V fragments feed three MFMAs, 236 registers) while the head dim
     // leaves room for them at two waves per SIMD (dh <= 80): 1.26 -> 1.17 ms at N = T = 4096, dh 72
     int wide = (int64_t)((N + 127) / 128) * H * B >= 1024;
     if (dh <= 80 && (int64_t)((N + 191) / 192) * H * B >= 1024) wide = 2;
-    static const int wide4 = YAT_TUNE_INT("YAT_SDPA_WIDE4", 1);
-    if (wide4 && !key_bias && dh <= 80 && (int64_t)((N + 255) / 256) * H * B >= 1024) wide = 3;    // (no-bias ONES classes only)
+    // ... and 256-query ones in the no-bias ONES classes (profiles/r03_c_attention_qs3_vs_qs4.txt)
+    if (!key_bias && dh <= 80 && (int64_t)((N + 255) / 256) * H * B >= 1024) wide = 3;
     if (wide_env >= 0) wide = wide_env;
     if (!key_bias) {
         const int rc = launch_fwd_nobias(p, B, wide, (hipStream_t)stream);
         if (rc != -100) return rc;
     }
-    return YAT_SDPA_DISPATCH(launch_fwd, dh, p, B, wide, (hipStream_t)stream);
+    return SDPA_DISPATCH(launch_fwd, dh, p, B, wide, (hipStream_t)stream);
 }
 
 int sdpa_bwd_impl(int B, int N, int T, int H, int dh, float scale, const void* q, int ldq, const void* k, const void* v,
@@ -1032,26 +931,20 @@ int sdpa_bwd_impl(int B, int N, int T, int H, int dh, float scale, const void* q
     if (!key_bias && (kv_len || kv_off || work_list)) return YAT_EINVAL;
     if ((uint64_t)B * N * lddo * 2 > 0x7fffffffull) return YAT_EINVAL;
     if (kv_off && !kv_len) return YAT_EINVAL;
-    SdpaP p{};
-    p.N = N; p.T = T; p.H = H; p.dh = dh; p.scale = scale;
-    p.q = (const bf16_t*)q; p.ldq = ldq; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.ldkv = ldkv;
-    p.bias = key_bias; p.kv_len = kv_len; p.out = (bf16_t*)out; p.ldo = ldo; p.lse = (float*)lse; p.kv_off = kv_off;
+    SdpaP p = common_params(B, N, T, H, dh, scale, q, ldq, k, v, ldkv, kv_off, kv_rows, key_bias, kv_len, out, ldo, lse);
     p.dout = (const bf16_t*)dout; p.lddo = lddo; p.delta = delta; p.dq = (bf16_t*)dq; p.lddq = lddq;
     p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv; p.lddkv = lddkv;
-    p.q_bytes = (uint64_t)B * N * ldq * 2; p.kv_bytes = (uint64_t)kv_rows * ldkv * 2; p.do_bytes = (uint64_t)B * N * lddo * 2;
-    p.bias_bytes = (uint64_t)B * T * 4;
+    p.do_bytes = (uint64_t)B * N * lddo * 2;
     p.stat_bytes = (uint64_t)B * H * N * 4;
-    static const int xcd_env = YAT_TUNE_INT("YAT_SDPA_XCD", -1);
-    p.xcd_remap = xcd_env >= 0 ? xcd_env : (T >= 1024);
     if (parts < 1 || parts > 3) return YAT_EINVAL;
     static const int wide_env = YAT_TUNE_INT("YAT_SDPA_WIDE", -1);
     if (parts & 1) {                               // dQ, and delta = rowsum(dO * O) which the dK/dV part reads
         // (three sub-tiles per wave with the key tile walked in halves fit -- 254 registers at dh 72 -- but measured only
         //  -2.4 % at N = T = 4096 and +5 % on the T = 300 cross-attention: not instantiated)
         int wide = wide_env >= 0 ? wide_env : ((int64_t)((N + 127) / 128) * H * B >= 1024);
-        static const int dq3 = YAT_TUNE_INT("YAT_SDPA_DQ3", 1);      // dh 64, L = 4429: 1524 -> 1421 us (profiles/r03_f)
-        if (dq3 && wide_env < 0 && dh <= 64 && (int64_t)((N + 191) / 192) * H * B >= 1024) wide = 2;
-        const int rc = YAT_SDPA_DISPATCH(launch_dq, dh, p, B, wide, (hipStream_t)stream);
+        // 192-query workgroups: dh 64, L = 4429: 1524 -> 1421 us (profiles/r03_f)
+        if (wide_env < 0 && dh <= 64 && (int64_t)((N + 191) / 192) * H * B >= 1024) wide = 2;
+        const int rc = SDPA_DISPATCH(launch_dq, dh, p, B, wide, (hipStream_t)stream);
         if (rc != YAT_OK) return rc;
     }
     if (!(parts & 2)) return YAT_OK;
@@ -1060,20 +953,15 @@ int sdpa_bwd_impl(int B, int N, int T, int H, int dh, float scale, const void* q
         // the compact list's units are single key tiles (equal work): an XCD-contiguous order is balanced whatever the lengths and
         // puts the key tiles of one (image, head) -- which read the same Q / dO -- on one L2: 67.3 -> 56.8 us on the ragged
         // SANA batch (round 6, profiles/r06_b_cross_attention_xcd_order.txt; the list path ran unmapped before)
-        static const int xcd_work = YAT_TUNE_INT("YAT_SDPA_XCD_WORK", 1);
-        p.xcd_remap = xcd_work;
+        p.xcd_remap = 1;
     }
-    // 128-key workgroups: dense grid only (the host's compact work list counts 64-key tiles)
-    // dK/dV: 128-key workgroups of 4 waves x 32 keys (code 2) on the dense grid (the host's compact work list counts 64-key
+    // dK/dV: 128-key workgroups of 4 waves x 32 keys on the dense grid (the host's compact work list counts 64-key
     // tiles) while the head dim leaves the registers for two waves per SIMD (dh <= 80: 222 VGPRs once the query tile is
     // walked in two 32-row halves): every Q / dO fragment read from LDS feeds two MFMAs -- 1.83 -> 1.42 ms at N = T = 4096,
-    // dh 72.  (Same shape with all four 16-query tiles in flight: 330 registers, one wave per SIMD, 3.19 vs 2.37 ms; code 1 =
-    // 8 waves x 16 keys: 1.97 vs 1.80 ms.  Both stay reachable through YAT_SDPA_WIDE_KV.)
-    static const int wide_kv_env = YAT_TUNE_INT("YAT_SDPA_WIDE_KV", -1);
-    int wide_kv = (dh <= 80 && (int64_t)((T + 127) / 128) * H * B >= 1024) ? 2 : 0;
-    if (wide_kv_env >= 0) wide_kv = wide_kv_env;
-    if (p.work) wide_kv = 0;
-    return YAT_SDPA_DISPATCH(launch_dkv, dh, p, B, wide_kv, (hipStream_t)stream);
+    // dh 72.  (Same shape with all four 16-query tiles in flight: 330 registers, one wave per SIMD, 3.19 vs 2.37 ms; 8 waves x
+    // 16 keys: 1.97 vs 1.80 ms.)
+    const bool wide_kv = !p.work && dh <= 80 && (int64_t)((T + 127) / 128) * H * B >= 1024;
+    return SDPA_DISPATCH(launch_dkv, dh, p, B, wide_kv, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -1109,12 +997,3 @@ int yat_sdpa_bwd_packed(int B, int N, int T, int H, int dh, float scale, const v
 }
 
 }  // extern "C"
-
-#ifdef YAT_SDPA_STAMPS
-extern "C" int yat_debug_sdpa_wg_times(unsigned int* host_dst) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(yat_sdpa_wg_times), sizeof(unsigned int) * 4096 * 6);
-}
-extern "C" int yat_debug_sdpa_stamps(unsigned int* host_dst) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(yat_sdpa_stamp_buf), sizeof(unsigned int) * 136);
-}
-#endif
