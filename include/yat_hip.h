@@ -155,7 +155,10 @@ int yat_ln_modulate_bwd(int M, int D, int rows_per_batch, const void* x, const f
                         yat_stream_t stream);
 
 /* RMSNorm with affine weight, eps inside the sqrt (caption_norm, patched_sana_transformer.py:136,298)
- *   y = bf16( bf16(x * rsqrt(mean(x^2) + eps)) * w ).   bwd: dx, dw (bf16, optional accumulate). */
+ *   y = bf16( bf16(x * rsqrt(mean(x^2) + eps)) * w ).   bwd: dx, dw (bf16, optional accumulate).
+ * These two are the one-segment, compact-row case of yat_rmsnorm_seg_fwd / _bwd below (nseg = 1, every leading dimension D,
+ * no keep) and run the same kernels: the same bits, and yat_rmsnorm_bwd_workspace_bytes(M, D) ==
+ * yat_rmsnorm_seg_bwd_workspace_bytes(M, D, 1).  dw and workspace are required here. */
 uint64_t yat_rmsnorm_bwd_workspace_bytes(int M, int D);
 int yat_rmsnorm_fwd(int M, int D, float eps, const void* x, const void* w, void* y, float* rstd, yat_stream_t stream);
 int yat_rmsnorm_bwd(int M, int D, const void* x, const void* w, const float* rstd, const void* dy, void* dx,

@@ -26,7 +26,8 @@ BYTES = [            # (regex on the kernel name, algorithmic bytes per call, wh
     (r"ln_mod_fwd", 4 * M * D, "x read, h written"),
     (r"ln_mod_bwd_rows", 8 * M * D, "dy, x, incoming dx read; dx written"),
     (r"ln_mod_bwd_cols", 4 * M * D, "dy, x read (column statistics)"),
-    (r"strip_kernel<1>", 6 * M * D, "gate backward: dout, lin read; dlin written"),
+    (r"gate_bwd_strip_kernel", 6 * M * D, "gate backward: dout, lin read; dlin written"),
+    (r"colsum_strip_kernel", 2 * M * D, "bias gradient not fused into a wgrad: an [M, D] dy read (the text-side calls read less)"),
     (r"sdpa_fwd", 4 * M * D, "cross-attention: q read, o written (k, v: text rows, small)"),
     (r"sdpa_bwd_dq", 8 * M * D, "q, do, o read; dq written"),
     (r"sdpa_bwd_dkv", 4 * M * D, "q, do read (dk, dv: text rows)"),

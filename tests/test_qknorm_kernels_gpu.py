@@ -193,22 +193,28 @@ def test_rmsnorm_seg_fwd_bwd(ops, D, M, nseg):
         guard_intact(rxw, rx, f"{tag} raw input", SENT if keep else NAN)
 
 
-@pytest.mark.parametrize("D", [72, 2240, 4096])
-def test_one_segment_is_the_plain_rmsnorm(ops, D):
-    """nseg = 1 on compact rows is yat_rmsnorm_fwd / _bwd: y, rstd and dx bit for bit (the same arithmetic); dw is the same sum
-    of the same terms grouped per workgroup instead of per wave before its one bf16 rounding (close, defaults)."""
-    M = 37
+@pytest.mark.parametrize("accumulate_dw", [False, True])
+@pytest.mark.parametrize("D,M", [(72, 37), (2240, 37), (4096, 37), (72, 4115)])
+def test_one_segment_is_the_plain_rmsnorm(ops, D, M, accumulate_dw):
+    """yat_rmsnorm_fwd / _bwd are the segment kernels at nseg = 1 on compact rows: y, rstd, dx and dw bit for bit, dw written
+    plainly and accumulated onto a non-zero prior, out of a workspace of the same declared size.  One MAXV class each at 37
+    rows, and 4115 rows of 72 columns: 258 row groups on the 256 workgroups of the backward, so two workgroups walk a second
+    group and one of these a ragged one."""
     x, dy, w = rnd(M, D, scale=1.5, seed=24), rnd(M, D, seed=25), (1 + 0.1 * rnd(D, seed=26).float()).to(BF)
     y0, r0 = ops.rmsnorm_fwd(x, w, EPS)
     y1, r1 = torch.empty_like(x), torch.empty(M, dtype=torch.float32, device=DEV)
     ops.rmsnorm_seg_fwd(x, [w], EPS, y1, r1)
     same(y1, y0, "y")
     same(r1, r0, "rstd")
-    dx0, dw0, dx1, dw1 = (torch.empty_like(t) for t in (x, w, x, w))
-    ops.rmsnorm_bwd(x, w, r0, dy, dx0, dw0, wspace(ops._lib().yat_rmsnorm_bwd_workspace_bytes(M, D)))
-    ops.rmsnorm_seg_bwd(x, [w], r1, dy, dx1, [dw1], wspace(ops.rmsnorm_seg_bwd_workspace_bytes(M, D, 1)))
+    nbytes = ops._lib().yat_rmsnorm_bwd_workspace_bytes(M, D)
+    assert nbytes == ops.rmsnorm_seg_bwd_workspace_bytes(M, D, 1)
+    prior = rnd(D, scale=2.0, seed=27)
+    dx0, dx1 = torch.empty_like(x), torch.empty_like(x)
+    dw0, dw1 = (prior.clone() if accumulate_dw else torch.full((D,), NAN, dtype=BF, device=DEV) for _ in range(2))
+    ops.rmsnorm_bwd(x, w, r0, dy, dx0, dw0, wspace(nbytes), accumulate_dw=accumulate_dw)
+    ops.rmsnorm_seg_bwd(x, [w], r1, dy, dx1, [dw1], wspace(nbytes), accumulate_dw=accumulate_dw)
     same(dx1, dx0, "dx")
-    close(dw1, dw0, "dw against yat_rmsnorm_bwd")
+    same(dw1, dw0, f"dw acc={int(accumulate_dw)}")
 
 
 # ------------------------------------------------------------------------------------------------ argument rejection

@@ -375,8 +375,9 @@ def _ws_contract(nbytes, run, name):
     print(f"[parity] {name}: {nbytes} workspace bytes, {len(results[0])} outputs compared")
 
 
-@pytest.mark.parametrize("M,D", [(5, 72), (67, 2568)])
+@pytest.mark.parametrize("M,D", [(5, 72), (67, 2568), (4115, 72)])
 def test_workspace_rmsnorm_bwd(ops, M, D):
+    """(4115 rows: 258 groups of 16 rows on the 256 workgroups the backward is capped at -- one partial row per workgroup)"""
     x, dy, w = rnd(M, D, scale=1.5, seed=24), rnd(M, D, seed=25), (1 + 0.1 * rnd(D, seed=26).float()).to(BF)
     _, rstd = ops.rmsnorm_fwd(x, w, 1e-5)
 

@@ -142,13 +142,39 @@ __global__ __launch_bounds__(256) void ln_mod_bwd_rows_kernel(int M, int D, int 
     }
 }
 
+// Epilogue of the strip-layout kernels (a lane owns 8 of the workgroup's 512 columns and has summed NSET quantities over its
+// wave's rows): the four waves meet in LDS and are summed in wave order, 256 threads x 2 columns, into ONE partial row per
+// workgroup and set -- the follow-up reduction reads 4x less.  acc[s]: the lane's 8 sums of set s; out[s]: column 0 of set s's
+// partial row, a null one is not written.  The kernels sum into one 8-float array per quantity and copy them into `acc` for
+// the call: summing into a [2][8] array (or handing over pointers to the arrays) made the compiler vectorize the row loops
+// another way -- ln_mod_bwd_cols_kernel went from 191 to 215 (256) VGPRs.
+template <int NSET>
+__device__ __forceinline__ void strip_partial_row(const float (&acc)[NSET][8], int ncols, float* const (&out)[NSET]) {
+    __shared__ float red[NSET * WAVES * 512];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+#pragma unroll
+        for (int s = 0; s < NSET; ++s) red[(s * WAVES + wave) * 512 + lane * 8 + e] = acc[s][e];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int cl = threadIdx.x + 256 * k, c = blockIdx.x * 512 + cl;
+        if (c >= ncols) continue;
+#pragma unroll
+        for (int s = 0; s < NSET; ++s) {
+            const float* r = red + s * WAVES * 512 + cl;
+            if (out[s]) out[s][c] = r[0] + r[512] + r[1024] + r[1536];
+        }
+    }
+}
+
 // grid = (ceil(D/512), ceil(rpb / (WAVES * LN_COL_ROWS)), B); one partial row per workgroup: ws[(b*gridDim.y + by)][2][D].
 // Eight rows' loads (x, dy, mean, rstd) are issued before the first use: with one row in flight per wave the 1280 waves of
 // a 8192 x 2240 gradient kept 2.6 MB in flight, a quarter of what the HBM pipe needs (3.7 TB/s measured).
 constexpr int LN_COL_ROWS = 16;
 __global__ __launch_bounds__(256) void ln_mod_bwd_cols_kernel(int rpb, int D, const bf16_t* x, const float* mean_in,
                                                               const float* rstd_in, const bf16_t* dy, float* ws) {
-    __shared__ float red[2 * WAVES * 512];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c0 = blockIdx.x * 512 + lane * 8;
     const int b = blockIdx.z;
@@ -181,20 +207,12 @@ __global__ __launch_bounds__(256) void ln_mod_bwd_cols_kernel(int rpb, int D, co
             }
         }
     }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        red[wave * 512 + lane * 8 + e] = a1[e];
-        red[(WAVES + wave) * 512 + lane * 8 + e] = a2[e];
-    }
-    __syncthreads();
     float* wp = ws + ((int64_t)b * gridDim.y + blockIdx.y) * 2 * D;
+    float acc[2][8];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int cl = threadIdx.x + 256 * k, c = blockIdx.x * 512 + cl;
-        if (c >= D) continue;
-        wp[c] = red[cl] + red[512 + cl] + red[1024 + cl] + red[1536 + cl];
-        wp[D + c] = red[2048 + cl] + red[2560 + cl] + red[3072 + cl] + red[3584 + cl];
-    }
+    for (int e = 0; e < 8; ++e) { acc[0][e] = a1[e]; acc[1][e] = a2[e]; }
+    float* const out[2] = {wp, wp + D};
+    strip_partial_row<2>(acc, D, out);
 }
 
 // Partial-row reductions: a 256-thread block owns 64 columns; 4 thread rows split the G partial rows and meet in LDS
@@ -221,113 +239,29 @@ __global__ __launch_bounds__(256) void reduce_partials_f32_kernel(int B, int G, 
     else if (out1) out1[(int64_t)b * ld_out + (j - half)] += s;
 }
 
-// bf16 output variant (bias / weight gradients): out[j] = (accumulate ? out[j] : 0) + sum_g ws[g*W + j]
-__global__ __launch_bounds__(256) void reduce_partials_bf16_kernel(int G, int W, const float* ws, bf16_t* out,
-                                                                   int accumulate) {
+// bf16 output variant (bias / weight gradients), one grid row per segment: grid = (ceil(W / 64), nseg), segment s sums
+// ws[s][G][W] into out0 (s = 0) or out1 (s = 1; unused with one segment): out[j] = (accumulate ? out[j] : 0) + sum_g ws[g*W + j]
+__global__ __launch_bounds__(256) void reduce_partials_bf16_kernel(int G, int W, const float* ws, bf16_t* out0,
+                                                                   bf16_t* out1, int accumulate) {
     const int j = blockIdx.x * 64 + (threadIdx.x & 63);
-    float s = reduce_rows64(ws, G, W, j, j < W);
+    bf16_t* out = blockIdx.y ? out1 : out0;
+    float s = reduce_rows64(ws + (int64_t)blockIdx.y * G * W, G, W, j, j < W);
     if (threadIdx.x >= 64 || j >= W) return;
     if (accumulate) s = rbf(s) + bf2f(out[j]);
     out[j] = f2bf(s);
 }
 
-// ------------------------------------------------------------------ RMSNorm
-template <int MAXV>
-__global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(int M, int D, float eps, const bf16_t* x, const bf16_t* w,
-                                                          bf16_t* y, float* rstd_out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int row = blockIdx.x * WAVES + wave;
-    if (row >= M) return;
-    const int nchunk = D >> 3;
-    float v[MAXV][8];
-    load_row<MAXV>(x + (int64_t)row * D, nchunk, lane, v);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) q += v[i][e] * v[i][e];
-    const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-    if (lane == 0) rstd_out[row] = rstd;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nchunk) {
-            float ww[8], o[8];
-            unpack8(*reinterpret_cast<const u32x4*>(w + c * 8), ww);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = rbf(v[i][e] * rstd) * ww[e];
-            *reinterpret_cast<u32x4*>(y + (int64_t)row * D + c * 8) = pack8(o);
-        }
-    }
-}
-
-// grid.x = ceil(M / 16); partial rows ws[(blk*4 + wave)][D] hold dw partials
-template <int MAXV>
-__global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(int M, int D, const bf16_t* x, const bf16_t* w,
-                                                          const float* rstd_in, const bf16_t* dy, bf16_t* dx,
-                                                          float* ws) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nchunk = D >> 3;
-    float ww[MAXV][8], aw[MAXV][8];
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nchunk) unpack8(*reinterpret_cast<const u32x4*>(w + c * 8), ww[i]);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { aw[i][e] = 0.f; if (c >= nchunk) ww[i][e] = 0.f; }
-    }
-    const int r_begin = blockIdx.x * (WAVES * ROWS_PER_WAVE) + wave * ROWS_PER_WAVE;
-    for (int rr = 0; rr < ROWS_PER_WAVE; ++rr) {
-        const int64_t row = r_begin + rr;
-        if (row >= M) break;
-        float v[MAXV][8], g[MAXV][8];
-        load_row<MAXV>(x + row * D, nchunk, lane, v);
-        load_row<MAXV>(dy + row * D, nchunk, lane, g);
-        const float rstd = rstd_in[row];
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < MAXV; ++i)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float xn = v[i][e] * rstd;
-                aw[i][e] += g[i][e] * rbf(xn);
-                const float gg = rbf(g[i][e] * ww[i][e]);
-                v[i][e] = xn; g[i][e] = gg;
-                s += gg * xn;
-            }
-        s = wave_sum(s) / (float)D;
-#pragma unroll
-        for (int i = 0; i < MAXV; ++i) {
-            const int c = lane + 64 * i;
-            if (c < nchunk) {
-                float o[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = rstd * (g[i][e] - v[i][e] * s);
-                *reinterpret_cast<u32x4*>(dx + row * D + c * 8) = pack8(o);
-            }
-        }
-    }
-    float* wp = ws + ((int64_t)blockIdx.x * WAVES + wave) * D;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nchunk) {
-#pragma unroll
-            for (int e = 0; e < 8; e += 4)
-                *reinterpret_cast<f32x4*>(wp + c * 8 + e) = f32x4{aw[i][e], aw[i][e + 1], aw[i][e + 2], aw[i][e + 3]};
-        }
-    }
-}
-
-// ------------------------------------------------------------------ RMSNorm over strided row segments (q/k norm)
+// ------------------------------------------------------------------ RMSNorm over strided row segments
+// The one RMSNorm kernel pair: the q/k norm of SANA-1.5 (nseg = 2 on a fused projection) and, at nseg = 1 on compact rows
+// (ld = D) with no `keep`, the plain yat_rmsnorm_fwd / _bwd of the caption norm.
 // One wave owns one (row, segment): segment s of row r starts at x + r * ldx + s * D and has its own weight.  The segment is
 // in registers before the first store, so y may be x (in place on the q|k columns of a fused projection); `keep` (nullable)
-// receives the raw values compactly, [M, nseg * D], for the backward.  Arithmetic and rounding points: rmsnorm_fwd_kernel.
+// receives the raw values compactly, [M, nseg * D], for the backward.
 template <int MAXV>
 __global__ __launch_bounds__(256) void rmsnorm_seg_fwd_kernel(int M, int D, int nseg, float eps, const bf16_t* x, int ldx,
                                                               const bf16_t* w0, const bf16_t* w1, bf16_t* y, int ldy,
                                                               bf16_t* keep, float* rstd_out) {
-    // product and sum stay two roundings, as rmsnorm_fwd_kernel is compiled: rstd is then the plain kernel's bit for bit
+    // product and sum stay two roundings: a fused multiply-add here would move rstd, and with it every y, by a bit
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t task = (int64_t)blockIdx.x * WAVES + wave;
@@ -361,12 +295,12 @@ __global__ __launch_bounds__(256) void rmsnorm_seg_fwd_kernel(int M, int D, int 
     }
 }
 
-// grid = (seg_bwd_blocks(M), nseg); a workgroup strides over the 16-row groups, a wave walks ROWS_PER_WAVE rows of each like
-// rmsnorm_bwd_kernel (same two roundings); dx may be dy (the row's dy is in registers before the first store).  The fused
+// grid = (seg_bwd_blocks(M), nseg); a workgroup strides over the 16-row groups, a wave walks ROWS_PER_WAVE rows of each;
+// dx may be dy (the row's dy is in registers before the first store).  The fused
 // multiply-adds are written out: left to the compiler, the <.., false> instantiation (rows unrolled four times) summed
 // gg * xn as a packed multiply and an add where <.., true> used a fused one, and the dx of the two differed in the last bit.  DW: the four
 // waves' column sums meet in LDS in wave order and leave ONE partial row per workgroup, ws[seg][blk][D] -- at the step's
-// 8192 rows the 2048 per-wave rows of rmsnorm_bwd_kernel's scheme made the follow-up reduction (18 MB per segment through 35
+// 8192 rows one partial row per wave (2048 of them) made the follow-up reduction (18 MB per segment through 35
 // workgroups, 110 us) dearer than this kernel.
 constexpr int SEG_BWD_MAX_BLOCKS = 256;          // one workgroup per CU; 1024 waves x 2 rows of loads in flight
 inline int seg_bwd_blocks(int M) {
@@ -452,38 +386,17 @@ __global__ __launch_bounds__(256) void rmsnorm_seg_bwd_kernel(int M, int D, cons
     }
 }
 
-// reduce_partials_bf16_kernel per segment: grid = (ceil(W / 64), nseg), segment s sums ws[s][G][W] into out0 / out1
-__global__ __launch_bounds__(256) void reduce_partials_seg_bf16_kernel(int G, int W, const float* ws, bf16_t* out0,
-                                                                       bf16_t* out1, int accumulate) {
-    const int j = blockIdx.x * 64 + (threadIdx.x & 63);
-    bf16_t* out = blockIdx.y ? out1 : out0;
-    float s = reduce_rows64(ws + (int64_t)blockIdx.y * G * W, G, W, j, j < W);
-    if (threadIdx.x >= 64 || j >= W) return;
-    if (accumulate) s = rbf(s) + bf2f(out[j]);
-    out[j] = f2bf(s);
-}
-
 // ------------------------------------------------------------------ strip kernels (512 columns x 32 rows per wave)
 constexpr int STRIP_ROWS = 32;            // rows per wave of the column sum
 constexpr int GATE_ROWS = 16;             // ... of the gate backward (three streams per row: twice the workgroups)
-// MODE 0: column sum of x.  MODE 1: gate backward: dlin = bf16(gate*dout), partial = dout*lin, and (ws2 != null) the
-// column sum of dlin, i.e. the bias gradient of the gated Linear, for free.
-// The four waves of a workgroup are summed in LDS: one partial row per workgroup (the follow-up reduction reads 4x less).
-template <int MODE>
-__global__ __launch_bounds__(256) void strip_kernel(int rows_per_batch, int cols, const bf16_t* x, int ld,
-                                                    const bf16_t* lin, const bf16_t* gate, int gate_ld, bf16_t* dlin,
-                                                    float* ws, float* ws2) {
-    // grid = (ceil(cols/512), ceil(rpb / 128), B)
-    __shared__ float red[(MODE == 1 ? 2 : 1) * WAVES * 512];
+
+// Column sum of x[rows, cols]: grid = (ceil(cols/512), ceil(rows / (WAVES * STRIP_ROWS))), partial rows ws[blockIdx.y][cols].
+__global__ __launch_bounds__(256) void colsum_strip_kernel(int rows, int cols, const bf16_t* x, int ld, float* ws) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c0 = blockIdx.x * 512 + lane * 8;
-    const int b = blockIdx.z;
-    const int rg = blockIdx.y * WAVES + wave;                 // row group within the batch
-    constexpr int SR = MODE == 1 ? GATE_ROWS : STRIP_ROWS;
-    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, acc2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    float g[8];
-    if (MODE == 1 && c0 < cols) unpack8(*reinterpret_cast<const u32x4*>(gate + (int64_t)b * gate_ld + c0), g);
-    if (MODE == 0 && c0 < cols) {
+    const int rg = blockIdx.y * WAVES + wave;                 // row group
+    float acc[1][8] = {};
+    if (c0 < cols) {
         // eight rows' loads in flight per lane before the first add (a wave of this kernel is alone on its SIMD more often
         // than not: 320 workgroups on 256 CUs for an 8192 x 2240 gradient); the adds keep the row order, so the sums are
         // bit-identical to the one-row-at-a-time loop
@@ -492,59 +405,66 @@ __global__ __launch_bounds__(256) void strip_kernel(int rows_per_batch, int cols
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const int rl = rg * STRIP_ROWS + r0 + q;
-                v[q] = rl < rows_per_batch ? *reinterpret_cast<const u32x4*>(x + ((int64_t)b * rows_per_batch + rl) * ld + c0)
-                                           : u32x4{0u, 0u, 0u, 0u};
+                v[q] = rl < rows ? *reinterpret_cast<const u32x4*>(x + (int64_t)rl * ld + c0) : u32x4{0u, 0u, 0u, 0u};
             }
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 float a[8];
                 unpack8(v[q], a);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) acc[e] += a[e];
+                for (int e = 0; e < 8; ++e) acc[0][e] += a[e];
             }
         }
-    } else if (c0 < cols) {
-        // gate backward: the same eight-rows-in-flight shape (x and lin: 16 loads per lane before the first multiply)
-        for (int r0 = 0; r0 < SR; r0 += 8) {
+    }
+    float* const out[1] = {ws + (int64_t)blockIdx.y * cols};
+    strip_partial_row<1>(acc, cols, out);
+}
+
+// Gate backward on compact [B * rows_per_batch, cols] rows: dlin = bf16(gate * dout), partial rows of dout * lin (the gate
+// gradient) in ws and, with ws2 != null, of dlin (the bias gradient of the gated Linear, for free) in ws2.
+// grid = (ceil(cols/512), ceil(rpb / (WAVES * GATE_ROWS)), B); partial row (batch, row block) of ws[..][cols], ws2[..][cols].
+__global__ __launch_bounds__(256) void gate_bwd_strip_kernel(int rows_per_batch, int cols, const bf16_t* dout,
+                                                             const bf16_t* lin, const bf16_t* gate, int gate_ld,
+                                                             bf16_t* dlin, float* ws, float* ws2) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c0 = blockIdx.x * 512 + lane * 8;
+    const int b = blockIdx.z;
+    const int rg = blockIdx.y * WAVES + wave;                 // row group within the batch
+    float dg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, db[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // dgate terms, dbias terms
+    if (c0 < cols) {
+        float g[8];
+        unpack8(*reinterpret_cast<const u32x4*>(gate + (int64_t)b * gate_ld + c0), g);
+        // the column sum's eight-rows-in-flight shape (dout and lin: 16 loads per lane before the first multiply)
+        for (int r0 = 0; r0 < GATE_ROWS; r0 += 8) {
             u32x4 va[8], vl[8];
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                const int rl = rg * SR + r0 + q;
+                const int rl = rg * GATE_ROWS + r0 + q;
                 const int64_t row = (int64_t)b * rows_per_batch + rl;
                 const bool in = rl < rows_per_batch;
-                va[q] = in ? *reinterpret_cast<const u32x4*>(x + row * ld + c0) : u32x4{0u, 0u, 0u, 0u};
-                vl[q] = in ? *reinterpret_cast<const u32x4*>(lin + row * ld + c0) : u32x4{0u, 0u, 0u, 0u};
+                va[q] = in ? *reinterpret_cast<const u32x4*>(dout + row * cols + c0) : u32x4{0u, 0u, 0u, 0u};
+                vl[q] = in ? *reinterpret_cast<const u32x4*>(lin + row * cols + c0) : u32x4{0u, 0u, 0u, 0u};
             }
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                const int rl = rg * SR + r0 + q;
+                const int rl = rg * GATE_ROWS + r0 + q;
                 if (rl >= rows_per_batch) continue;
                 const int64_t row = (int64_t)b * rows_per_batch + rl;
                 float a[8], l[8], o[8];
                 unpack8(va[q], a);
                 unpack8(vl[q], l);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { acc[e] += rbf(a[e] * l[e]); o[e] = rbf(g[e] * a[e]); acc2[e] += o[e]; }
-                *reinterpret_cast<u32x4*>(dlin + row * ld + c0) = pack8(o);
+                for (int e = 0; e < 8; ++e) { dg[e] += rbf(a[e] * l[e]); o[e] = rbf(g[e] * a[e]); db[e] += o[e]; }
+                *reinterpret_cast<u32x4*>(dlin + row * cols + c0) = pack8(o);
             }
         }
     }
+    const int64_t part = (int64_t)(gridDim.y * blockIdx.z + blockIdx.y) * cols;
+    float acc[2][8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        red[wave * 512 + lane * 8 + e] = acc[e];
-        if (MODE == 1) red[(WAVES + wave) * 512 + lane * 8 + e] = acc2[e];
-    }
-    __syncthreads();
-    // 256 threads x 2 columns
-    const int part = (int)(gridDim.y * blockIdx.z + blockIdx.y);     // partial row: (batch, row block)
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int cl = threadIdx.x + 256 * k, c = blockIdx.x * 512 + cl;
-        if (c >= cols) continue;
-        ws[(int64_t)part * cols + c] = red[cl] + red[512 + cl] + red[1024 + cl] + red[1536 + cl];
-        if (MODE == 1 && ws2)
-            ws2[(int64_t)part * cols + c] = red[2048 + cl] + red[2560 + cl] + red[3072 + cl] + red[3584 + cl];
-    }
+    for (int e = 0; e < 8; ++e) { acc[0][e] = dg[e]; acc[1][e] = db[e]; }
+    float* const out[2] = {ws + part, ws2 ? ws2 + part : nullptr};
+    strip_partial_row<2>(acc, cols, out);
 }
 
 // ------------------------------------------------------------------ modulation table
@@ -644,38 +564,56 @@ int yat_ln_modulate_bwd(int M, int D, int rpb, const void* x, const float* mean,
     return YAT_OK;
 }
 
-int yat_rmsnorm_fwd(int M, int D, float eps, const void* x, const void* w, void* y, float* rstd, yat_stream_t stream) {
-    if (M <= 0 || !x || !w || !y || !rstd) return YAT_EINVAL;
+// The one launch site of each RMSNorm kernel (and of the reduce behind the backward); the entries below check the arguments.
+static int launch_rmsnorm_fwd(int M, int D, int nseg, float eps, const void* x, int ldx, const void* w0, const void* w1,
+                              void* y, int ldy, void* keep, float* rstd, yat_stream_t stream) {
+    const int64_t tasks = (int64_t)M * nseg;
     return dispatch_maxv(D, [&](auto mv) {
         constexpr int MV = decltype(mv)::value;
-        hipLaunchKernelGGL((rmsnorm_fwd_kernel<MV>), dim3((M + WAVES - 1) / WAVES), dim3(256), 0, (hipStream_t)stream, M,
-                           D, eps, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, rstd);
+        hipLaunchKernelGGL((rmsnorm_seg_fwd_kernel<MV>), dim3((unsigned)((tasks + WAVES - 1) / WAVES)), dim3(256), 0,
+                           (hipStream_t)stream, M, D, nseg, eps, (const bf16_t*)x, ldx, (const bf16_t*)w0, (const bf16_t*)w1,
+                           (bf16_t*)y, ldy, (bf16_t*)keep, rstd);
         YAT_CHECK_LAUNCH();
         return YAT_OK;
     });
 }
 
+// dw0 null: dx only (no workspace, no reduce)
+static int launch_rmsnorm_bwd(int M, int D, int nseg, const void* x, int ldx, const void* w0, const void* w1,
+                              const float* rstd, const void* dy, int lddy, void* dx, int lddx, void* dw0, void* dw1,
+                              int accumulate_dw, void* workspace, yat_stream_t stream) {
+    const bool want_dw = dw0 != nullptr;
+    const int nblk = seg_bwd_blocks(M);
+    int rc = dispatch_maxv(D, [&](auto mv) {
+        constexpr int MV = decltype(mv)::value;
+        hipLaunchKernelGGL((want_dw ? rmsnorm_seg_bwd_kernel<MV, true> : rmsnorm_seg_bwd_kernel<MV, false>), dim3(nblk, nseg),
+                           dim3(256), 0, (hipStream_t)stream, M, D, (const bf16_t*)x, ldx, (const bf16_t*)w0, (const bf16_t*)w1,
+                           rstd, (const bf16_t*)dy, lddy, (bf16_t*)dx, lddx, (float*)workspace);
+        YAT_CHECK_LAUNCH();
+        return YAT_OK;
+    });
+    if (rc || !want_dw) return rc;
+    hipLaunchKernelGGL(reduce_partials_bf16_kernel, dim3((D + 63) / 64, nseg), dim3(256), 0, (hipStream_t)stream, nblk, D,
+                       (const float*)workspace, (bf16_t*)dw0, (bf16_t*)dw1, accumulate_dw);
+    YAT_CHECK_LAUNCH();
+    return YAT_OK;
+}
+
+// yat_rmsnorm_fwd / _bwd: the one-segment, compact-row case (nseg = 1, every leading dimension D, no raw copy) of the
+// segment kernels -- same arithmetic, same workspace.
+int yat_rmsnorm_fwd(int M, int D, float eps, const void* x, const void* w, void* y, float* rstd, yat_stream_t stream) {
+    if (M <= 0 || !x || !w || !y || !rstd) return YAT_EINVAL;
+    return launch_rmsnorm_fwd(M, D, 1, eps, x, D, w, nullptr, y, D, nullptr, rstd, stream);
+}
+
 uint64_t yat_rmsnorm_bwd_workspace_bytes(int M, int D) {
-    return (uint64_t)((M + WAVES * ROWS_PER_WAVE - 1) / (WAVES * ROWS_PER_WAVE)) * WAVES * D * sizeof(float);
+    return (uint64_t)seg_bwd_blocks(M) * D * sizeof(float);                     // one partial row per workgroup
 }
 
 int yat_rmsnorm_bwd(int M, int D, const void* x, const void* w, const float* rstd, const void* dy, void* dx,
                     void* dw, int accumulate_dw, void* workspace, yat_stream_t stream) {
     if (M <= 0 || !x || !w || !rstd || !dy || !dx || !dw || !workspace) return YAT_EINVAL;
-    const int nblk = (M + WAVES * ROWS_PER_WAVE - 1) / (WAVES * ROWS_PER_WAVE);
-    int rc = dispatch_maxv(D, [&](auto mv) {
-        constexpr int MV = decltype(mv)::value;
-        hipLaunchKernelGGL((rmsnorm_bwd_kernel<MV>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, M, D,
-                           (const bf16_t*)x, (const bf16_t*)w, rstd, (const bf16_t*)dy, (bf16_t*)dx, (float*)workspace);
-        YAT_CHECK_LAUNCH();
-        return YAT_OK;
-    });
-    if (rc) return rc;
-    // rows past M never wrote their partial row: zero-filled? no -- every wave writes its (possibly zero) partials
-    hipLaunchKernelGGL(reduce_partials_bf16_kernel, dim3((D + 63) / 64), dim3(256), 0, (hipStream_t)stream,
-                       nblk * WAVES, D, (const float*)workspace, (bf16_t*)dw, accumulate_dw);
-    YAT_CHECK_LAUNCH();
-    return YAT_OK;
+    return launch_rmsnorm_bwd(M, D, 1, x, D, w, nullptr, rstd, dy, D, dx, D, dw, nullptr, accumulate_dw, workspace, stream);
 }
 
 static bool seg_args_bad(int M, int D, int nseg, int ld) {
@@ -686,15 +624,7 @@ int yat_rmsnorm_seg_fwd(int M, int D, int nseg, float eps, const void* x, int ld
                         int ldy, void* keep, float* rstd, yat_stream_t stream) {
     if (seg_args_bad(M, D, nseg, ldx) || seg_args_bad(M, D, nseg, ldy) || !x || !w0 || (nseg == 2 && !w1) || !y || !rstd)
         return YAT_EINVAL;
-    const int64_t tasks = (int64_t)M * nseg;
-    return dispatch_maxv(D, [&](auto mv) {
-        constexpr int MV = decltype(mv)::value;
-        hipLaunchKernelGGL((rmsnorm_seg_fwd_kernel<MV>), dim3((unsigned)((tasks + WAVES - 1) / WAVES)), dim3(256), 0,
-                           (hipStream_t)stream, M, D, nseg, eps, (const bf16_t*)x, ldx, (const bf16_t*)w0, (const bf16_t*)w1,
-                           (bf16_t*)y, ldy, (bf16_t*)keep, rstd);
-        YAT_CHECK_LAUNCH();
-        return YAT_OK;
-    });
+    return launch_rmsnorm_fwd(M, D, nseg, eps, x, ldx, w0, w1, y, ldy, keep, rstd, stream);
 }
 
 uint64_t yat_rmsnorm_seg_bwd_workspace_bytes(int M, int D, int nseg) {
@@ -711,25 +641,7 @@ int yat_rmsnorm_seg_bwd(int M, int D, int nseg, const void* x, int ldx, const vo
     const bool want_dw = dw0 != nullptr;                      // a frozen base under adapters passes no dw at all
     if (nseg == 2 && want_dw != (dw1 != nullptr)) return YAT_EINVAL;
     if (want_dw && !workspace) return YAT_EINVAL;
-    const int nblk = seg_bwd_blocks(M);
-    int rc = dispatch_maxv(D, [&](auto mv) {
-        constexpr int MV = decltype(mv)::value;
-        if (want_dw)
-            hipLaunchKernelGGL((rmsnorm_seg_bwd_kernel<MV, true>), dim3(nblk, nseg), dim3(256), 0, (hipStream_t)stream, M, D,
-                               (const bf16_t*)x, ldx, (const bf16_t*)w0, (const bf16_t*)w1, rstd, (const bf16_t*)dy, lddy,
-                               (bf16_t*)dx, lddx, (float*)workspace);
-        else
-            hipLaunchKernelGGL((rmsnorm_seg_bwd_kernel<MV, false>), dim3(nblk, nseg), dim3(256), 0, (hipStream_t)stream, M, D,
-                               (const bf16_t*)x, ldx, (const bf16_t*)w0, (const bf16_t*)w1, rstd, (const bf16_t*)dy, lddy,
-                               (bf16_t*)dx, lddx, (float*)nullptr);
-        YAT_CHECK_LAUNCH();
-        return YAT_OK;
-    });
-    if (rc || !want_dw) return rc;
-    hipLaunchKernelGGL(reduce_partials_seg_bf16_kernel, dim3((D + 63) / 64, nseg), dim3(256), 0, (hipStream_t)stream,
-                       nblk, D, (const float*)workspace, (bf16_t*)dw0, (bf16_t*)dw1, accumulate_dw);
-    YAT_CHECK_LAUNCH();
-    return YAT_OK;
+    return launch_rmsnorm_bwd(M, D, nseg, x, ldx, w0, w1, rstd, dy, lddy, dx, lddx, dw0, dw1, accumulate_dw, workspace, stream);
 }
 
 uint64_t yat_colsum_workspace_bytes(int rows, int cols) {
@@ -741,12 +653,11 @@ int yat_colsum_bf16(int rows, int cols, const void* x, int ld, void* out, int ac
                     yat_stream_t stream) {
     if (rows <= 0 || cols <= 0 || (cols & 7) || (ld & 7) || !x || !out || !workspace) return YAT_EINVAL;
     const int gy = (rows + WAVES * STRIP_ROWS - 1) / (WAVES * STRIP_ROWS);
-    hipLaunchKernelGGL((strip_kernel<0>), dim3((cols + 511) / 512, gy, 1), dim3(256), 0, (hipStream_t)stream, rows, cols,
-                       (const bf16_t*)x, ld, (const bf16_t*)nullptr, (const bf16_t*)nullptr, 0, (bf16_t*)nullptr,
-                       (float*)workspace, (float*)nullptr);
+    hipLaunchKernelGGL(colsum_strip_kernel, dim3((cols + 511) / 512, gy), dim3(256), 0, (hipStream_t)stream, rows, cols,
+                       (const bf16_t*)x, ld, (float*)workspace);
     YAT_CHECK_LAUNCH();
     hipLaunchKernelGGL(reduce_partials_bf16_kernel, dim3((cols + 63) / 64), dim3(256), 0, (hipStream_t)stream, gy, cols,
-                       (const float*)workspace, (bf16_t*)out, accumulate);
+                       (const float*)workspace, (bf16_t*)out, (bf16_t*)nullptr, accumulate);      // one segment: no out1
     YAT_CHECK_LAUNCH();
     return YAT_OK;
 }
@@ -765,8 +676,8 @@ int yat_gate_bwd(int M, int D, int rpb, const void* dout, const void* lin, const
     const int B = M / rpb;
     const int gy = (rpb + WAVES * GATE_ROWS - 1) / (WAVES * GATE_ROWS);
     float* ws2 = dbias ? (float*)workspace + (int64_t)B * gy * D : nullptr;
-    hipLaunchKernelGGL((strip_kernel<1>), dim3((D + 511) / 512, gy, B), dim3(256), 0, (hipStream_t)stream, rpb, D,
-                       (const bf16_t*)dout, D, (const bf16_t*)lin, (const bf16_t*)gate, gate_ld, (bf16_t*)dlin,
+    hipLaunchKernelGGL(gate_bwd_strip_kernel, dim3((D + 511) / 512, gy, B), dim3(256), 0, (hipStream_t)stream, rpb, D,
+                       (const bf16_t*)dout, (const bf16_t*)lin, (const bf16_t*)gate, gate_ld, (bf16_t*)dlin,
                        (float*)workspace, ws2);
     YAT_CHECK_LAUNCH();
     hipLaunchKernelGGL(reduce_partials_f32_kernel, dim3((D + 63) / 64, B), dim3(256), 0, (hipStream_t)stream, B, gy, D,
@@ -774,7 +685,7 @@ int yat_gate_bwd(int M, int D, int rpb, const void* dout, const void* lin, const
     YAT_CHECK_LAUNCH();
     if (dbias) {                                              // bias gradient of the gated Linear = column sum of dlin
         hipLaunchKernelGGL(reduce_partials_bf16_kernel, dim3((D + 63) / 64), dim3(256), 0, (hipStream_t)stream, B * gy, D,
-                           (const float*)ws2, (bf16_t*)dbias, accumulate_bias);
+                           (const float*)ws2, (bf16_t*)dbias, (bf16_t*)nullptr, accumulate_bias);
         YAT_CHECK_LAUNCH();
     }
     return YAT_OK;
