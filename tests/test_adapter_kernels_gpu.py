@@ -386,9 +386,9 @@ def _hadamard(ops, rows, cols, lds, offs, scales, seed):
 
 @pytest.mark.parametrize("rows,cols", [(5, 8), (33, 72)])
 def test_hadamard_every_stride_differs(rows, cols):
-    """hadamard_kernel<0 / 1> at 5 x 8 (one chunk per row: five live threads) and 33 x 72 (9 chunks per row, 297 chunks: two
-    workgroups, the second ragged), every operand and result a column block of a differently padded matrix, so that all of
-    lda / ldb / ldo and ldd / ld1 / ld2 / ldt1 / ldt2 differ."""
+    """hadamard_scale_kernel / hadamard_bwd_kernel at 5 x 8 (one chunk per row: five live threads) and 33 x 72 (9 chunks per row,
+    297 chunks: two workgroups, the second ragged), every operand and result a column block of a differently padded matrix, so
+    that all of lda / ldb / ldo and ldd / ld1 / ld2 / ldt1 / ldt2 differ."""
     from yat_amd import ops
     lds = [cols + 8 * k for k in (1, 3, 2, 5, 4, 6)]
     offs = [8, 0, 16, 24, 8, 40]
@@ -405,8 +405,8 @@ def test_hadamard_grid_wrap():
 # --------------------------------------------------------------------------------- 10. yat_dora_delta / yat_dora_bwd
 @pytest.mark.parametrize("cols", [8, 2048, 2056, 2240, 5600])
 def test_dora_row_loops(cols):
-    """dora_kernel<0 / 1>, one workgroup per row, 256 threads x 8 columns per pass of the row loops: cols / 8 = 1 (one live
-    thread), 256 (one pass, exactly full), 257 and 280 (two passes), 700 (three).  W, lw, dd, delta and t1 are column blocks of
+    """dora_delta_kernel / dora_bwd_kernel, one workgroup per row, 256 threads x 8 columns per pass of the row loops: cols / 8 =
+    1 (one live thread), 256 (one pass, exactly full), 257 and 280 (two passes), 700 (three).  W, lw, dd, delta and t1 are column blocks of
     wider matrices (inputs NaN-padded, results NaN-filled).  Integer W, lw, dd and scaling 0.5: u = W + lw / 2 is exact, and
     so are sum u^2 (multiples of 1/4: below 2^22) and sum dd u (multiples of 1/2: below 2^23) in any order.
     n, s: the criteria of test_dora_row_kernels_match_torch (one bf16 step on n, two on s).  Given the device's own s and n:

@@ -1,14 +1,23 @@
-// LoKr adapter support kernels for gfx950 (BASELINE config 5: ``lora_algo: lokr`` -> peft LoKrConfig(r, alpha,
-// module_dropout, target_modules) wrapped around the model at /root/reference/common/trainer.py:212-238).
+// Adapter support kernels for gfx950: what the trainer's four peft adapter families (``lora_algo``: lokr, lora, loha, and lora
+// with use_dora) need beside the GEMM kernels of this library.  The dense products (x delta_w^T, dy delta_w, d_delta = dy^T x)
+// are GEMMs; what is left is HBM-bound glue, all in the module dtype (bf16) with every op rounding as torch's does.
 //
-// [RECALL peft/tuners/lokr/layer.py]  For a target Linear / 1x1 Conv with weight [out, in]:
+// LoKr  [RECALL peft/tuners/lokr/layer.py]  For a target Linear / 1x1 Conv with weight [out, in]:
 //   (out_l, out_k) = factorization(out), (in_m, in_n) = factorization(in);  w1 [out_l, in_m] (zeros at init),
 //   w2 = w2_a [out_k, r] @ w2_b [r, in_n] (both kaiming-uniform);  delta_w = kron(w1, w2) * (alpha / r);
-//   forward: base_layer(x) + F.linear(x, delta_w)   -- all in the module dtype (bf16), every op rounding.
-// The dense products (x delta_w^T, dy delta_w, d_delta = dy^T x) run on the GEMM kernels of this library; what is left
-// is HBM-bound glue, one launch per adapter:
+//   forward: base_layer(x) + F.linear(x, delta_w).
 //   yat_lokr_delta   : w2 = bf16(w2_a w2_b);  delta[(i,k),(j,n)] = bf16( bf16(w1[i,j] * w2[k,n]) * scale )
 //   yat_lokr_project : autograd of the above from d_delta: d_w1, d_w2 (fp32 sums, fixed order), d_w2_a, d_w2_b.
+//   yat_lokr_rows, yat_lokr_rows_fwd_flat : the factored path's row products with w2_b (T1 = x' w2_b^T, dx' += H' w2_b).
+// Rank-R products of the factored LoKr path and of plain LoRA, R = 8, 16 (FMA streams) and 32, 64, 128 (matrix cores):
+//   yat_rank_expand      : io = f(h w) over a whole layer width.
+//   yat_lokr_small_wgrad : out (+)= a^T x -- R x N outputs of a million-row reduction, fixed-order fp32 partials.
+//   yat_lora_scatter_b   : scaling * lora_B^T of every adapter into the shadow of the flat weights.
+// LoHa  : yat_hadamard_scale (delta_w), yat_hadamard_bwd (the element-wise half of its backward).
+// DoRA  : yat_dora_delta (norm, scale and delta per output row), yat_dora_bwd (d_magnitude and the scaled d_delta).
+#include <initializer_list>
+#include <type_traits>
+
 #include "common.hpp"
 #include "../../include/yat_hip.h"
 
@@ -37,9 +46,17 @@ __global__ __launch_bounds__(256) void lokr_delta_kernel(LokrP p, bf16_t* delta)
     delta[(int64_t)row * p.ld + col] = f2bf(v);
 }
 
+// sum of `v` over the 256 threads of the workgroup, on every thread: wave_sum, then the four waves in order through LDS
+__device__ __forceinline__ float block_sum(float v) {
+    __shared__ float red[4];
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
 // d_w1[i,j] = sum_{k,n} dR[(i,k),(j,n)] * w2[k,n],  dR = bf16(d_delta * scale).  One workgroup per (i,j).
 __global__ __launch_bounds__(256) void lokr_dw1_kernel(LokrP p, const bf16_t* dd, bf16_t* dw1) {
-    __shared__ float red[4];
     const int j = blockIdx.x, i = blockIdx.y;
     float s = 0.f;
     const int per = p.out_k * p.in_n;
@@ -49,10 +66,8 @@ __global__ __launch_bounds__(256) void lokr_dw1_kernel(LokrP p, const bf16_t* dd
         if (p.scale != 1.0f) g = rbf(g * p.scale);
         s += g * w2_elem(p, k, n);
     }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) dw1[i * p.in_m + j] = f2bf(red[0] + red[1] + red[2] + red[3]);
+    s = block_sum(s);
+    if (threadIdx.x == 0) dw1[i * p.in_m + j] = f2bf(s);
 }
 
 // partial[i][k*in_n + n] = sum_j dR[(i,k),(j,n)] * w1[i,j]   (one workgroup per i; summed over i by the next kernel)
@@ -100,14 +115,22 @@ __global__ __launch_bounds__(256) void lokr_dw2_final_kernel(LokrP p, const floa
 // Small-output weight gradient of the factored adapter path: out[q, n] (+)= sum_row A[row, q] * X[row, n] with a few
 // (R <= 16) x (N <= 128) outputs and a million-row reduction (rows = B*N_tokens*in_m) -- far outside what a tiled GEMM is
 // for.  HBM-bound streaming pass; every workgroup leaves one fp32 partial, a second launch sums the partials in a fixed
-// order (no atomics).  (v1 -- a wave per row, a lane per column pair -- was latency-bound: 226-477 us per call.)
-// v3: the reduction runs on the matrix cores.  out^T tile = a^T x is a 16 x 128 MFMA accumulator block (q padded to 16, eight
-// 16-column tiles), k = 32 rows per v_mfma_f32_16x16x32_bf16; both operands are "k-strided" (k = the row index is the slow
-// dimension of a and x), so a workgroup stages CH rows of each as row-major LDS images with 16-byte loads and the waves
-// fetch fragments with the hardware-transposing ds_read_b64_tr_b16 (the x image XOR-swizzled like gemm256's k-strided
-// operand, the 32-byte rows of the a image need no swizzle).  The pass is a stream through LDS: 16 MFMAs per wave per 256 rows.
-// (v1, a wave per row: 226-477 us per call; v2, scalar FMAs from LDS: ~200 us in the step; traffic alone is ~35 us.)
+// order (no atomics).  The reduction runs on the matrix cores: out^T tile = a^T x is a 16 x 128 MFMA accumulator block (q
+// padded to 16, eight 16-column tiles), k = 32 rows per v_mfma_f32_16x16x32_bf16; both operands are "k-strided" (k = the row
+// index is the slow dimension of a and x), so a workgroup stages CH rows of each as row-major LDS images with 16-byte loads
+// and the waves fetch fragments with the hardware-transposing ds_read_b64_tr_b16 (the x image XOR-swizzled like gemm256's
+// k-strided operand, the 32-byte rows of the a image need no swizzle).  The pass is a stream through LDS: 16 MFMAs per wave
+// per 256 rows.  (What came before it and what each took: DESIGN.md, "Plain LoRA up to rank 128".)
 __device__ __forceinline__ uint32_t sw_swz(uint32_t krow) { return ((krow & 3) | (((krow >> 3) & 1) << 2)) << 1; }
+
+// The x image of both weight-gradient kernels: [CH][128] bf16, 256-byte rows, the 16-byte piece c of row r at c ^ sw_swz(r).
+// Lane (g, 4 q + p)'s MFMA fragment of it: rows ra = 32 kk + 8 g + q and rb = ra + 4, columns 8 piece + 4 (p & 1) ..
+// (The staging of the image stays written out in each kernel: moved into a shared load / store pair, the R = 64 kernel
+// measured 1.3 % slower in three rounds out of three, profiles/lokr_fold_a_bench.txt.)
+__device__ __forceinline__ bf16x8 x_frag(const char* ximg, uint32_t ra, uint32_t rb, uint32_t piece, uint32_t p) {
+    return cat4(lds_read_tr4(ximg, ra * 256 + ((piece ^ sw_swz(ra)) << 4) + (p & 1) * 8),
+                lds_read_tr4(ximg, rb * 256 + ((piece ^ sw_swz(rb)) << 4) + (p & 1) * 8));
+}
 
 __global__ __launch_bounds__(256) void lokr_small_wgrad_kernel(int64_t rows, int R, int N, int ldx, int npad, const bf16_t* A,
                                                                const bf16_t* X, float* partial) {
@@ -130,7 +153,7 @@ __global__ __launch_bounds__(256) void lokr_small_wgrad_kernel(int64_t rows, int
         const int nr = (int)(rows - r0 < CH ? rows - r0 : CH);
         // Stage the chunk with every global load in flight before the first LDS store: as a plain loop (runtime trip count,
         // load -> store per iteration) the compiler serialised up to 16 dependent round trips to memory per chunk and the
-        // kernel ran at 0.9 TB/s of its 168 MB (round 4; the rank-8, in_n = 56 adapter gradients of BASELINE config 5).
+        // kernel ran at 0.9 TB/s of its 168 MB.
         u32x4 xv[16], av[2];
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -167,13 +190,8 @@ __global__ __launch_bounds__(256) void lokr_small_wgrad_kernel(int64_t rows, int
             const bf16x8 af = cat4(lds_read_tr4(aimg, ra * 32 + p * 8), lds_read_tr4(aimg, rb * 32 + p * 8));
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
-                if (t < ntile) {
-                    const uint32_t col = t * 16 + 4 * p;
-                    const uint32_t ca = (col >> 3) ^ sw_swz(ra), cb = (col >> 3) ^ sw_swz(rb);
-                    const bf16x8 xf = cat4(lds_read_tr4(ximg, ra * 256 + ca * 16 + (p & 1) * 8),
-                                           lds_read_tr4(ximg, rb * 256 + cb * 16 + (p & 1) * 8));
-                    acc[t] = mfma16(af, xf, acc[t]);         // acc[t][r] @ lane (g, li): out[q = 4g + r][n = 16t + li]
-                }
+                if (t < ntile)                               // acc[t][r] @ lane (g, li): out[q = 4g + r][n = 16t + li]
+                    acc[t] = mfma16(af, x_frag(ximg, ra, rb, 2 * t + (p >> 1), p), acc[t]);
             }
         }
     }
@@ -274,6 +292,38 @@ __global__ __launch_bounds__(256) void lokr_rows_fwd_kernel(int64_t rows, int N,
 // its 8 columns from w2_b in LDS (fp32, per-chunk columns) and updates the chunk in place, no exchange.  (v1 gave a lane a whole
 // row: every 16-byte load of a wave touched 64 different rows, 245 us per call against ~65 us of traffic; v2 padded a row to 8 or
 // 16 lanes: 6 of 16 idle at in_n = 80, 3.2 TB/s.)
+// The rank-R FMA stream of the two kernels below: o[0..8) = sum_q hrow[q] * w[q * wstride + 0..8), q ascending, hrow = R bf16
+// of one row in global memory, w = this thread's 8 columns of the fp32 image of w in LDS.
+template <int R>
+__device__ __forceinline__ void rank_fma8(const bf16_t* hrow, const float* w, int wstride, float (&o)[8]) {
+    float h[R];
+#pragma unroll
+    for (int v = 0; v < R / 8; ++v) unpack8(*reinterpret_cast<const u32x4*>(hrow + v * 8), h + v * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = 0.f;
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+        const f32x4 lo = *reinterpret_cast<const f32x4*>(w + q * wstride), hi = *reinterpret_cast<const f32x4*>(w + q * wstride + 4);
+        o[0] += h[q] * lo[0]; o[1] += h[q] * lo[1]; o[2] += h[q] * lo[2]; o[3] += h[q] * lo[3];
+        o[4] += h[q] * hi[0]; o[5] += h[q] * hi[1]; o[6] += h[q] * hi[2]; o[7] += h[q] * hi[3];
+    }
+}
+// ... and their epilogue on the 16 bytes at dp:
+//   residual = 0: io = bf16(bf16(sum) * scale)      (peft: lora_B(..) * scaling, each op rounded)
+//   residual = 1: io = bf16(bf16(sum) + io)         (accumulation into an input gradient, the GEMM's residual rounding)
+__device__ __forceinline__ void expand_store8(float (&o)[8], bf16_t* dp, float scale, int residual) {
+    if (residual) {
+        float d[8];
+        unpack8(*reinterpret_cast<const u32x4*>(dp), d);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = rbf(o[e]) + d[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = rbf(o[e]) * scale;
+    }
+    *reinterpret_cast<u32x4*>(dp) = pack8(o);
+}
+
 template <int R>
 __global__ __launch_bounds__(256) void lokr_rows_bwd_kernel(uint32_t chunks, int N, const bf16_t* wb, const bf16_t* a, bf16_t* io) {
     __shared__ float w[R][128];
@@ -282,20 +332,9 @@ __global__ __launch_bounds__(256) void lokr_rows_bwd_kernel(uint32_t chunks, int
     const uint32_t cpr = (uint32_t)N >> 3;                     // chunks per row
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < chunks; i += gridDim.x * 256u) {
         const uint32_t row = i / cpr, n = (i - row * cpr) * 8;
-        float h[R], o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, d[8];
-#pragma unroll
-        for (int v = 0; v < R / 8; ++v) unpack8(*reinterpret_cast<const u32x4*>(a + (int64_t)row * R + v * 8), h + v * 8);
-#pragma unroll
-        for (int q = 0; q < R; ++q) {
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(&w[q][n]), hi = *reinterpret_cast<const f32x4*>(&w[q][n + 4]);
-            o[0] += h[q] * lo[0]; o[1] += h[q] * lo[1]; o[2] += h[q] * lo[2]; o[3] += h[q] * lo[3];
-            o[4] += h[q] * hi[0]; o[5] += h[q] * hi[1]; o[6] += h[q] * hi[2]; o[7] += h[q] * hi[3];
-        }
-        bf16_t* dp = io + (int64_t)i * 8;
-        unpack8(*reinterpret_cast<const u32x4*>(dp), d);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = rbf(o[e]) + d[e];
-        *reinterpret_cast<u32x4*>(dp) = pack8(o);
+        float o[8];
+        rank_fma8<R>(a + (int64_t)row * R, &w[0][n], 128, o);
+        expand_store8(o, io + (int64_t)i * 8, 1.0f, 1);
     }
 }
 
@@ -319,9 +358,8 @@ __global__ __launch_bounds__(256) void lora_scatter_b_kernel(const int64_t* tabl
 }
 // Rank-R expansion over a whole layer width (plain LoRA: u = T B^T with K = R, dx += dT A): a GEMM with an 8-deep reduction
 // is all epilogue, so it runs as a stream instead -- io[row, n] = f(sum_q h[row, q] * w[q, n]) with w's column block
-// (CB = 512 columns, fp32) in LDS, a lane per 16-byte chunk of the output row, a wave per 512 contiguous columns.
-//   residual = 0: io = bf16(bf16(sum) * scale)      (peft: lora_B(..) * scaling, each op rounded)
-//   residual = 1: io = bf16(bf16(sum) + io)         (accumulation into an input gradient, the GEMM's residual rounding)
+// (CB = 512 columns, fp32) in LDS, a lane per 16-byte chunk of the output row, a wave per 512 contiguous columns; f and
+// `residual` as at expand_store8.
 template <int R>
 __global__ __launch_bounds__(256) void lokr_wide_rows_kernel(int64_t rows, int N, int ldio, const bf16_t* wsrc, const bf16_t* h,
                                                              bf16_t* io, float scale, int residual) {
@@ -336,26 +374,9 @@ __global__ __launch_bounds__(256) void lokr_wide_rows_kernel(int64_t rows, int N
     const int c = threadIdx.x & 63, n = n0 + c * 8;          // this lane's 8 columns
     if (n >= N) return;
     for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += (int64_t)gridDim.x * 4) {
-        float hv[R], o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int v = 0; v < R / 8; ++v) unpack8(*reinterpret_cast<const u32x4*>(h + row * R + v * 8), hv + v * 8);
-#pragma unroll
-        for (int q = 0; q < R; ++q) {
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(&w[q][c * 8]), hi = *reinterpret_cast<const f32x4*>(&w[q][c * 8 + 4]);
-            o[0] += hv[q] * lo[0]; o[1] += hv[q] * lo[1]; o[2] += hv[q] * lo[2]; o[3] += hv[q] * lo[3];
-            o[4] += hv[q] * hi[0]; o[5] += hv[q] * hi[1]; o[6] += hv[q] * hi[2]; o[7] += hv[q] * hi[3];
-        }
-        bf16_t* dp = io + row * ldio + n;
-        if (residual) {
-            float d[8];
-            unpack8(*reinterpret_cast<const u32x4*>(dp), d);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = rbf(o[e]) + d[e];
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = rbf(o[e]) * scale;
-        }
-        *reinterpret_cast<u32x4*>(dp) = pack8(o);
+        float o[8];
+        rank_fma8<R>(h + row * R, &w[0][c * 8], CB, o);
+        expand_store8(o, io + row * ldio + n, scale, residual);
     }
 }
 
@@ -508,9 +529,7 @@ __global__ __launch_bounds__(256) void lora_wgrad_mfma_kernel(int64_t rows, int 
             for (int t = 0; t < CT; ++t) {
                 const int tt = wc * CT + t;
                 if (tt < ntile) {
-                    const uint32_t pc = 2 * tt + (p >> 1);
-                    const bf16x8 xf = cat4(lds_read_tr4(ximg, ra * 256 + ((pc ^ sw_swz(ra)) << 4) + (p & 1) * 8),
-                                           lds_read_tr4(ximg, rb * 256 + ((pc ^ sw_swz(rb)) << 4) + (p & 1) * 8));
+                    const bf16x8 xf = x_frag(ximg, ra, rb, 2 * tt + (p >> 1), p);
 #pragma unroll
                     for (int a = 0; a < QT; ++a) acc[a][t] = mfma16(af[a], xf, acc[a][t]);   // out[16 qtile + 4 g + r][16 tt + li]
                 }
@@ -530,23 +549,44 @@ __global__ __launch_bounds__(256) void lora_wgrad_mfma_kernel(int64_t rows, int 
         }
 }
 
-template <int R>
-int small_wgrad_mfma_launch(int G, int nblk, hipStream_t st, int64_t rows, int N, int ldx, int npad, const bf16_t* a,
-                            const bf16_t* x, float* ws) {
-    constexpr int lds = 128 * (256 + 2 * R);                 // x image 32 KiB + a image 8 / 16 / 32 KiB
+// Launch of a kernel with more than 64 KiB of dynamic LDS: the attribute that allows it is set once per kernel.
+template <auto Kernel, class... Args>
+int launch_big_lds(dim3 grid, int lds, hipStream_t st, Args... args) {
     static bool attr_set = false;
     if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)lora_wgrad_mfma_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-            hipSuccess)
+        if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
             return YAT_EINVAL;
         attr_set = true;
     }
-    hipLaunchKernelGGL((lora_wgrad_mfma_kernel<R>), dim3(G, nblk), dim3(256), lds, st, rows, N, ldx, npad, a, x, ws);
+    hipLaunchKernelGGL(Kernel, grid, dim3(256), lds, st, args...);
+    YAT_CHECK_LAUNCH();
     return YAT_OK;
 }
 
-// the padded ranks of plain LoRA (yat_rank_expand, yat_lokr_small_wgrad, yat_lora_scatter_b)
-bool rank_ok(int R) { return R == 8 || R == 16 || R == 32 || R == 64 || R == 128; }
+// The one dispatch on a runtime constant: with_const<8, 16, ..>(v, f) calls f(std::integral_constant<int, v>{}) for v in the
+// list (f returns a status) and is YAT_EINVAL for any other v.  with_rank: the padded ranks of plain LoRA (yat_rank_expand,
+// yat_lokr_small_wgrad, yat_lora_scatter_b); LoKr's own row products take the first two.
+template <int... Vs, class F>
+int with_const(int v, F f) {
+    int rc = YAT_EINVAL;
+    (void)((v == Vs ? (rc = f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+    return rc;
+}
+template <class F>
+int with_rank(int R, F f) { return with_const<8, 16, 32, 64, 128>(R, f); }
+bool rank_ok(int R) { return with_rank(R, [](auto) { return YAT_OK; }) == YAT_OK; }
+
+// `rows` x `cols` bf16 views read and written in 16-byte chunks: cols and every row stride a multiple of 8, no stride below cols
+bool views_ok(int rows, int cols, std::initializer_list<int> lds) {
+    bool ok = rows > 0 && cols > 0 && !(cols & 7);
+    for (int ld : lds) ok = ok && !(ld & 7) && ld >= cols;
+    return ok;
+}
+// grid of a kernel that strides over `units` work items, `per` of them per workgroup and step: at most 8192 workgroups
+dim3 chunk_grid(int64_t units, int per = 256) {
+    const int64_t g = (units + per - 1) / per;
+    return dim3((unsigned)(g > 8192 ? 8192 : g));
+}
 
 int fill(LokrP& p, int out_l, int out_k, int in_m, int in_n, int r, const void* w1, const void* w2a, const void* w2b,
          float scale, int ld) {
@@ -558,47 +598,92 @@ int fill(LokrP& p, int out_l, int out_k, int in_m, int in_n, int r, const void* 
     return YAT_OK;
 }
 
-
-// MODE 0: o1 = bf16(bf16(x * y) * scale).   MODE 1: g = bf16(x * scale); o1 = bf16(g * z); o2 = bf16(g * y)
-//         (x = d_delta, y = A1, z = A2 -> o1 = t1, o2 = t2).
-template <int MODE>
-__global__ __launch_bounds__(256) void hadamard_kernel(int rows, int cols, const bf16_t* x, int ldx, const bf16_t* y, int ldy,
-                                                       const bf16_t* z, int ldz, float scale, bf16_t* o1, int ld1, bf16_t* o2,
-                                                       int ld2) {
+// peft LoHa (HadaWeight [RECALL peft/tuners/loha/layer.py]): delta_w = ((w1a w1b) * (w2a w2b)) * scale, bf16 op by op, and the
+// element-wise half of its hand-written backward.  rows x cols views with row strides, a thread per 16-byte chunk.
+//   out = bf16(bf16(a * b) * scale)
+__global__ __launch_bounds__(256) void hadamard_scale_kernel(int rows, int cols, const bf16_t* a, int lda, const bf16_t* b, int ldb,
+                                                             float scale, bf16_t* out, int ldo) {
     const int cpr = cols >> 3;
     const int64_t total = (int64_t)rows * cpr;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t r = i / cpr;
         const int c = (int)(i - r * cpr) * 8;
-        float xv[8], yv[8], zv[8], a[8], b[8];
-        unpack8(*reinterpret_cast<const u32x4*>(x + r * ldx + c), xv);
-        unpack8(*reinterpret_cast<const u32x4*>(y + r * ldy + c), yv);
-        if (MODE == 1) unpack8(*reinterpret_cast<const u32x4*>(z + r * ldz + c), zv);
+        float av[8], bv[8], o[8];
+        unpack8(*reinterpret_cast<const u32x4*>(a + r * lda + c), av);
+        unpack8(*reinterpret_cast<const u32x4*>(b + r * ldb + c), bv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = rbf(rbf(av[e] * bv[e]) * scale);
+        *reinterpret_cast<u32x4*>(out + r * ldo + c) = pack8(o);
+    }
+}
+//   g = bf16(dd * scale);  t1 = bf16(g * a2);  t2 = bf16(g * a1)
+__global__ __launch_bounds__(256) void hadamard_bwd_kernel(int rows, int cols, const bf16_t* dd, int ldd, const bf16_t* a1, int ld1,
+                                                           const bf16_t* a2, int ld2, float scale, bf16_t* t1, int ldt1,
+                                                           bf16_t* t2, int ldt2) {
+    const int cpr = cols >> 3;
+    const int64_t total = (int64_t)rows * cpr;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / cpr;
+        const int c = (int)(i - r * cpr) * 8;
+        float dv[8], v1[8], v2[8], o1[8], o2[8];
+        unpack8(*reinterpret_cast<const u32x4*>(dd + r * ldd + c), dv);
+        unpack8(*reinterpret_cast<const u32x4*>(a1 + r * ld1 + c), v1);
+        unpack8(*reinterpret_cast<const u32x4*>(a2 + r * ld2 + c), v2);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            if (MODE == 0) a[e] = rbf(rbf(xv[e] * yv[e]) * scale);
-            else {
-                const float g = rbf(xv[e] * scale);
-                a[e] = rbf(g * zv[e]);
-                b[e] = rbf(g * yv[e]);
-            }
+            const float g = rbf(dv[e] * scale);
+            o1[e] = rbf(g * v2[e]);
+            o2[e] = rbf(g * v1[e]);
         }
-        *reinterpret_cast<u32x4*>(o1 + r * ld1 + c) = pack8(a);
-        if (MODE == 1) *reinterpret_cast<u32x4*>(o2 + r * ld2 + c) = pack8(b);
+        *reinterpret_cast<u32x4*>(t1 + r * ldt1 + c) = pack8(o1);
+        *reinterpret_cast<u32x4*>(t2 + r * ldt2 + c) = pack8(o2);
     }
 }
 
-// DoRA (peft LoraConfig(use_dora=True), common/trainer.py:215-220) [RECALL peft/tuners/lora/dora.py DoraLinearLayer]: with
-// lw = lora_B lora_A (bf16), u = bf16(W + bf16(scaling * lw)), n_j = bf16(||u_j||_2) (detached), s_j = bf16(m_j / n_j):
+// DoRA (peft LoraConfig(use_dora=True)) [RECALL peft/tuners/lora/dora.py DoraLinearLayer]: with lw = lora_B lora_A (bf16),
+// u = bf16(W + bf16(scaling * lw)), n_j = bf16(||u_j||_2) (detached), s_j = bf16(m_j / n_j):
 //   result = base(x) + (s - 1) (x W^T) + s scaling lora(x)  =  base(x) + x delta^T  with  delta_j = s_j (W_j + scaling lw_j) - W_j.
-// One workgroup per output row: pass 1 the norm, pass 2 the delta row (the row is re-read from L2).
-// MODE 0: delta + (s, n) out.  MODE 1 (backward): dm_j = (sum_l dd[j,l] u[j,l]) / n_j and t1 = bf16(s_j * scaling * dd).
-template <int MODE>
-__global__ __launch_bounds__(256) void dora_kernel(int cols, const bf16_t* W, int ldw, const bf16_t* lw, int ldl,
-                                                   const bf16_t* mag, float scaling, bf16_t* out, int ldo, float* s_buf,
-                                                   float* n_buf, const bf16_t* dd, int ldd, bf16_t* dmag) {
-    __shared__ float red[4];
+// One workgroup per output row j: pass 1 a sum over the row, pass 2 the output row (the row is re-read from L2).
+// (The row loop of pass 1 stays in each kernel and only block_sum is shared: with the loop inside any inlined helper the
+// compiler stops pairing its multiplies and roundings, 26 -> 29 VGPRs.)
+__device__ __forceinline__ float dora_u(float w, float l, float scaling) { return rbf(w + rbf(scaling * l)); }
+
+// delta_j as above; s_j and n_j are kept for the backward.
+__global__ __launch_bounds__(256) void dora_delta_kernel(int cols, const bf16_t* W, int ldw, const bf16_t* lw, int ldl,
+                                                         const bf16_t* mag, float scaling, bf16_t* delta, int ldd, float* s_buf,
+                                                         float* n_buf) {
     const int j = blockIdx.x, cpr = cols >> 3;
+    const bf16_t* wr = W + (int64_t)j * ldw;
+    const bf16_t* lr = lw + (int64_t)j * ldl;
+    float acc = 0.f;
+    for (int c = threadIdx.x; c < cpr; c += 256) {
+        float wv[8], lv[8];
+        unpack8(*reinterpret_cast<const u32x4*>(wr + c * 8), wv);
+        unpack8(*reinterpret_cast<const u32x4*>(lr + c * 8), lv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float u = dora_u(wv[e], lv[e], scaling);
+            acc += u * u;
+        }
+    }
+    const float tot = block_sum(acc);
+    const float n = rbf(sqrtf(tot)), s = rbf(bf2f(mag[j]) / n);
+    if (threadIdx.x == 0) { s_buf[j] = s; n_buf[j] = n; }
+    for (int c = threadIdx.x; c < cpr; c += 256) {
+        float wv[8], lv[8], a[8];
+        unpack8(*reinterpret_cast<const u32x4*>(wr + c * 8), wv);
+        unpack8(*reinterpret_cast<const u32x4*>(lr + c * 8), lv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] = s * (wv[e] + scaling * lv[e]) - wv[e];
+        *reinterpret_cast<u32x4*>(delta + (int64_t)j * ldd + c * 8) = pack8(a);
+    }
+}
+// backward: dm_j = (sum_l dd[j,l] u[j,l]) / n_j and t1 = bf16(bf16(s_j * scaling) * dd)
+__global__ __launch_bounds__(256) void dora_bwd_kernel(int cols, const bf16_t* dd, int ldd, const bf16_t* W, int ldw,
+                                                       const bf16_t* lw, int ldl, float scaling, const float* s_buf,
+                                                       const float* n_buf, bf16_t* t1, int ldt, bf16_t* dmag) {
+    const int j = blockIdx.x, cpr = cols >> 3;
+    const bf16_t* dr = dd + (int64_t)j * ldd;
     const bf16_t* wr = W + (int64_t)j * ldw;
     const bf16_t* lr = lw + (int64_t)j * ldl;
     float acc = 0.f;
@@ -606,44 +691,48 @@ __global__ __launch_bounds__(256) void dora_kernel(int cols, const bf16_t* W, in
         float wv[8], lv[8], dv[8];
         unpack8(*reinterpret_cast<const u32x4*>(wr + c * 8), wv);
         unpack8(*reinterpret_cast<const u32x4*>(lr + c * 8), lv);
-        if (MODE == 1) unpack8(*reinterpret_cast<const u32x4*>(dd + (int64_t)j * ldd + c * 8), dv);
+        unpack8(*reinterpret_cast<const u32x4*>(dr + c * 8), dv);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float u = rbf(wv[e] + rbf(scaling * lv[e]));
-            acc += MODE == 0 ? u * u : dv[e] * u;
-        }
+        for (int e = 0; e < 8; ++e) acc += dv[e] * dora_u(wv[e], lv[e], scaling);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    const float tot = red[0] + red[1] + red[2] + red[3];
-    float s, n;
-    if (MODE == 0) {
-        n = rbf(sqrtf(tot));
-        s = rbf(bf2f(mag[j]) / n);
-        if (threadIdx.x == 0) { s_buf[j] = s; n_buf[j] = n; }
-    } else {
-        s = s_buf[j];
-        n = n_buf[j];
-        if (threadIdx.x == 0) dmag[j] = f2bf(tot / n);
-    }
+    const float tot = block_sum(acc);
+    const float s = s_buf[j], n = n_buf[j];
+    if (threadIdx.x == 0) dmag[j] = f2bf(tot / n);
     for (int c = threadIdx.x; c < cpr; c += 256) {
-        float a[8];
-        if (MODE == 0) {
-            float wv[8], lv[8];
-            unpack8(*reinterpret_cast<const u32x4*>(wr + c * 8), wv);
-            unpack8(*reinterpret_cast<const u32x4*>(lr + c * 8), lv);
+        float dv[8], a[8];
+        unpack8(*reinterpret_cast<const u32x4*>(dr + c * 8), dv);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) a[e] = s * (wv[e] + scaling * lv[e]) - wv[e];
-        } else {
-            float dv[8];
-            unpack8(*reinterpret_cast<const u32x4*>(dd + (int64_t)j * ldd + c * 8), dv);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) a[e] = rbf(rbf(s * scaling) * dv[e]);
-        }
-        *reinterpret_cast<u32x4*>(out + (int64_t)j * ldo + c * 8) = pack8(a);
+        for (int e = 0; e < 8; ++e) a[e] = rbf(rbf(s * scaling) * dv[e]);
+        *reinterpret_cast<u32x4*>(t1 + (int64_t)j * ldt + c * 8) = pack8(a);
     }
+}
+
+// yat_lokr_rows and yat_lokr_rows_fwd_flat (im > 0: the flat layout)
+int lokr_rows_launch(int64_t rows, int N, int R, int backward, const void* w2_b, const void* a, void* io, int im, int ldt,
+                     yat_stream_t stream) {
+    if (rows <= 0 || (R != 8 && R != 16) || N <= 0 || N > 128 || (N & 7) || !w2_b || !a || !io) return YAT_EINVAL;
+    const bf16_t* wb = (const bf16_t*)w2_b;
+    const bf16_t* ap = (const bf16_t*)a;
+    bf16_t* iop = (bf16_t*)io;
+    hipStream_t st = (hipStream_t)stream;
+    if (!backward) {
+        const dim3 grid = chunk_grid((rows + 15) / 16, 16);                 // 4 waves x 4 row tiles per workgroup step
+        return with_const<1, 2, 3, 4>((N + 31) / 32, [&](auto ks) {
+            hipLaunchKernelGGL((lokr_rows_fwd_kernel<decltype(ks)::value>), grid, dim3(256), 0, st, rows, N, R, wb, ap, iop, im, ldt);
+            YAT_CHECK_LAUNCH();
+            return (int)YAT_OK;
+        });
+    }
+    const int64_t chunks = rows * (N >> 3);
+    const dim3 grid = chunk_grid(chunks);
+    // the kernel's chunk index is 32 bits wide and advances by grid * 256: the last live index plus one stride has to stay below
+    // 2^32, or the index wraps back under `chunks` and the loop never ends (chunks <= 2^32 - 2^21 at the capped grid)
+    if (chunks - 1 + (int64_t)grid.x * 256 > 0xffffffffll) return YAT_EINVAL;
+    return with_const<8, 16>(R, [&](auto rk) {
+        hipLaunchKernelGGL((lokr_rows_bwd_kernel<decltype(rk)::value>), grid, dim3(256), 0, st, (uint32_t)chunks, N, wb, ap, iop);
+        YAT_CHECK_LAUNCH();
+        return (int)YAT_OK;
+    });
 }
 
 }  // namespace
@@ -683,8 +772,6 @@ int yat_lokr_project(int out_l, int out_k, int in_m, int in_n, int r, const void
     return YAT_OK;
 }
 
-static int lokr_rows_launch(int64_t rows, int N, int R, int backward, const void* w2_b, const void* a, void* io, int im, int ldt,
-                            yat_stream_t stream);
 int yat_lokr_rows(int64_t rows, int N, int R, int backward, const void* w2_b, const void* a, void* io, yat_stream_t stream) {
     return lokr_rows_launch(rows, N, R, backward, w2_b, a, io, 0, 0, stream);
 }
@@ -693,73 +780,37 @@ int yat_lokr_rows_fwd_flat(int64_t rows, int N, int R, int in_m, const void* w2_
     if (in_m <= 0 || rows % in_m || (ldt & 7) || ldt < in_m * R) return YAT_EINVAL;
     return lokr_rows_launch(rows, N, R, 0, w2_b, x, t1_flat, in_m, ldt, stream);
 }
-static int lokr_rows_launch(int64_t rows, int N, int R, int backward, const void* w2_b, const void* a, void* io, int im, int ldt,
-                            yat_stream_t stream) {
-    if (rows <= 0 || (R != 8 && R != 16) || N <= 0 || N > 128 || (N & 7) || !w2_b || !a || !io) return YAT_EINVAL;
-    const bf16_t* wb = (const bf16_t*)w2_b;
-    const bf16_t* ap = (const bf16_t*)a;
-    bf16_t* iop = (bf16_t*)io;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 block(256);
-    if (!backward) {
-        const int64_t g64 = ((rows + 15) / 16 + 15) / 16;                   // 4 waves x 4 row tiles per workgroup step
-        const dim3 grid((unsigned)(g64 > 8192 ? 8192 : g64));
-#define YAT_FWD(KS) hipLaunchKernelGGL((lokr_rows_fwd_kernel<KS>), grid, block, 0, st, rows, N, R, wb, ap, iop, im, ldt)
-        if (N <= 32) YAT_FWD(1); else if (N <= 64) YAT_FWD(2); else if (N <= 96) YAT_FWD(3); else YAT_FWD(4);
-#undef YAT_FWD
-        YAT_CHECK_LAUNCH();
-        return YAT_OK;
-    }
-    const int64_t chunks = rows * (N >> 3);
-    const int64_t g64 = (chunks + 255) / 256;
-    const dim3 grid((unsigned)(g64 > 8192 ? 8192 : g64));
-    // the kernel's chunk index is 32 bits wide and advances by grid * 256: the last live index plus one stride has to stay below
-    // 2^32, or the index wraps back under `chunks` and the loop never ends (chunks <= 2^32 - 2^21 at the capped grid)
-    if (chunks - 1 + (int64_t)grid.x * 256 > 0xffffffffll) return YAT_EINVAL;
-    if (R == 8) hipLaunchKernelGGL((lokr_rows_bwd_kernel<8>), grid, block, 0, st, (uint32_t)chunks, N, wb, ap, iop);
-    else hipLaunchKernelGGL((lokr_rows_bwd_kernel<16>), grid, block, 0, st, (uint32_t)chunks, N, wb, ap, iop);
-    YAT_CHECK_LAUNCH();
-    return YAT_OK;
-}
 
 int yat_lora_scatter_b(int entries, int max_out, int R, float scale, const void* table, const void* src, void* dst,
                        yat_stream_t stream) {
     if (entries <= 0 || entries > 65535 || max_out <= 0 || !rank_ok(R) || !table || !src || !dst) return YAT_EINVAL;
-    const dim3 grid((max_out + 255) / 256, entries), block(256);
-#define YAT_SCATTER(RR) hipLaunchKernelGGL((lora_scatter_b_kernel<RR>), grid, block, 0, (hipStream_t)stream, (const int64_t*)table, \
-                                           scale, (const bf16_t*)src, (bf16_t*)dst)
-    if (R == 8) YAT_SCATTER(8); else if (R == 16) YAT_SCATTER(16); else if (R == 32) YAT_SCATTER(32);
-    else if (R == 64) YAT_SCATTER(64); else YAT_SCATTER(128);
-#undef YAT_SCATTER
-    YAT_CHECK_LAUNCH();
-    return YAT_OK;
+    return with_rank(R, [&](auto rk) {
+        hipLaunchKernelGGL((lora_scatter_b_kernel<decltype(rk)::value>), dim3((max_out + 255) / 256, entries), dim3(256), 0,
+                           (hipStream_t)stream, (const int64_t*)table, scale, (const bf16_t*)src, (bf16_t*)dst);
+        YAT_CHECK_LAUNCH();
+        return (int)YAT_OK;
+    });
 }
 
 int yat_rank_expand(int64_t rows, int N, int R, const void* w, const void* h, void* io, int ldio, float scale, int residual,
                     yat_stream_t stream) {
     if (rows <= 0 || !rank_ok(R) || N <= 0 || (N & 7) || (ldio & 7) || ldio < N || !w || !h || !io) return YAT_EINVAL;
-    if (R > 16) {                                            // matrix cores: 256-column blocks, 16-row tiles
-        const int nblk = (N + 255) / 256;
-        const int64_t tiles = (rows + 15) / 16;
-        const dim3 grid((unsigned)(tiles > 2048 / nblk + 1 ? 2048 / nblk + 1 : tiles), nblk);
-#define YAT_EXPAND(RR) hipLaunchKernelGGL((lora_expand_mfma_kernel<RR>), grid, dim3(256), 0, (hipStream_t)stream, rows, N, ldio, \
-                                          (const bf16_t*)w, (const bf16_t*)h, (bf16_t*)io, scale, residual)
-        if (R == 32) YAT_EXPAND(32); else if (R == 64) YAT_EXPAND(64); else YAT_EXPAND(128);
-#undef YAT_EXPAND
+    return with_rank(R, [&](auto rk) {
+        constexpr int RR = decltype(rk)::value;
+        // matrix cores: 256-column blocks, a workgroup step = one 16-row tile;  FMA stream: 512-column blocks, 4 rows
+        constexpr bool mfma = RR > 16;
+        const int nblk = mfma ? (N + 255) / 256 : (N + 511) / 512;
+        const int64_t steps = mfma ? (rows + 15) / 16 : (rows + 3) / 4;
+        const dim3 grid((unsigned)(steps > 2048 / nblk + 1 ? 2048 / nblk + 1 : steps), nblk);
+        if constexpr (mfma)
+            hipLaunchKernelGGL((lora_expand_mfma_kernel<RR>), grid, dim3(256), 0, (hipStream_t)stream, rows, N, ldio,
+                               (const bf16_t*)w, (const bf16_t*)h, (bf16_t*)io, scale, residual);
+        else
+            hipLaunchKernelGGL((lokr_wide_rows_kernel<RR>), grid, dim3(256), 0, (hipStream_t)stream, rows, N, ldio,
+                               (const bf16_t*)w, (const bf16_t*)h, (bf16_t*)io, scale, residual);
         YAT_CHECK_LAUNCH();
-        return YAT_OK;
-    }
-    const int nblk = (N + 511) / 512;
-    int64_t g64 = (rows + 3) / 4;
-    const int gx = (int)(g64 > 2048 / nblk + 1 ? 2048 / nblk + 1 : g64);
-    if (R == 8)
-        hipLaunchKernelGGL((lokr_wide_rows_kernel<8>), dim3(gx, nblk), dim3(256), 0, (hipStream_t)stream, rows, N, ldio,
-                           (const bf16_t*)w, (const bf16_t*)h, (bf16_t*)io, scale, residual);
-    else
-        hipLaunchKernelGGL((lokr_wide_rows_kernel<16>), dim3(gx, nblk), dim3(256), 0, (hipStream_t)stream, rows, N, ldio,
-                           (const bf16_t*)w, (const bf16_t*)h, (bf16_t*)io, scale, residual);
-    YAT_CHECK_LAUNCH();
-    return YAT_OK;
+        return (int)YAT_OK;
+    });
 }
 
 static int small_wgrad_groups(int64_t rows, int R, int nblk) {
@@ -787,92 +838,60 @@ int yat_lokr_small_wgrad(int64_t rows, int R, int N, int r_out, const void* a, c
         return YAT_EINVAL;
     const int nblk = (N + 127) / 128, npad = nblk * 128;
     const int G = small_wgrad_groups(rows, R, nblk);
-    const int n_out = r_out * N;
-    if (R > 16) {
-        hipStream_t st = (hipStream_t)stream;
-        const bf16_t* ap = (const bf16_t*)a;
-        const bf16_t* xp = (const bf16_t*)x;
-        float* ws = (float*)workspace;
-        const int rc = R == 32 ? small_wgrad_mfma_launch<32>(G, nblk, st, rows, N, ldx, npad, ap, xp, ws)
-                     : R == 64 ? small_wgrad_mfma_launch<64>(G, nblk, st, rows, N, ldx, npad, ap, xp, ws)
-                               : small_wgrad_mfma_launch<128>(G, nblk, st, rows, N, ldx, npad, ap, xp, ws);
-        if (rc != YAT_OK) return rc;
-        YAT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(lokr_small_wgrad_final_kernel, dim3((n_out + 15) / 16), dim3(256), 0, st, G, R, N, npad, r_out, scale,
-                           (const float*)workspace, (bf16_t*)out, ldo, accumulate);
-        YAT_CHECK_LAUNCH();
-        return YAT_OK;
-    }
-    const int lds = 256 * (128 + 16) * 2;                    // x image 64 KiB + a image 8 KiB
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)lokr_small_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 73728) !=
-            hipSuccess)
-            return YAT_EINVAL;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(lokr_small_wgrad_kernel, dim3(G, nblk), dim3(256), lds, (hipStream_t)stream, rows, R, N, ldx, npad,
-                       (const bf16_t*)a, (const bf16_t*)x, (float*)workspace);
-    YAT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(lokr_small_wgrad_final_kernel, dim3((n_out + 15) / 16), dim3(256), 0, (hipStream_t)stream, G, R, N, npad,
-                       r_out, scale, (const float*)workspace, (bf16_t*)out, ldo, accumulate);
+    hipStream_t st = (hipStream_t)stream;
+    const bf16_t* ap = (const bf16_t*)a;
+    const bf16_t* xp = (const bf16_t*)x;
+    float* ws = (float*)workspace;
+    const int rc = with_rank(R, [&](auto rk) {
+        constexpr int RR = decltype(rk)::value;
+        if constexpr (RR > 16)                               // x image 32 KiB + a image 8 / 16 / 32 KiB
+            return launch_big_lds<lora_wgrad_mfma_kernel<RR>>(dim3(G, nblk), 128 * (256 + 2 * RR), st, rows, N, ldx, npad, ap, xp, ws);
+        else                                                 // x image 64 KiB + a image 8 KiB
+            return launch_big_lds<lokr_small_wgrad_kernel>(dim3(G, nblk), 256 * (128 + 16) * 2, st, rows, R, N, ldx, npad, ap, xp, ws);
+    });
+    if (rc != YAT_OK) return rc;
+    hipLaunchKernelGGL(lokr_small_wgrad_final_kernel, dim3((r_out * N + 15) / 16), dim3(256), 0, st, G, R, N, npad, r_out, scale,
+                       (const float*)ws, (bf16_t*)out, ldo, accumulate);
     YAT_CHECK_LAUNCH();
     return YAT_OK;
 }
 
-
-// peft LoHa (HadaWeight [RECALL peft/tuners/loha/layer.py]): delta_w = ((w1a w1b) * (w2a w2b)) * scale, bf16 op by op, and
-// the element-wise half of its hand-written backward: g = dd * scale; t1 = g * A2; t2 = g * A1.  rows x cols views with row strides.
+// LoHa (the kernels' comment above).
 int yat_hadamard_scale(int rows, int cols, const void* a, int lda, const void* b, int ldb, float scale, void* out, int ldo,
                        yat_stream_t stream) {
-    if (rows <= 0 || cols <= 0 || (cols & 7) || (lda & 7) || (ldb & 7) || (ldo & 7) || lda < cols || ldb < cols || ldo < cols ||
-        !a || !b || !out)
-        return YAT_EINVAL;
-    const int64_t chunks = (int64_t)rows * (cols >> 3);
-    int64_t nb = (chunks + 255) / 256;
-    if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(hadamard_kernel<0>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, rows, cols, (const bf16_t*)a,
-                       lda, (const bf16_t*)b, ldb, (const bf16_t*)nullptr, 0, scale, (bf16_t*)out, ldo, (bf16_t*)nullptr, 0);
+    if (!views_ok(rows, cols, {lda, ldb, ldo}) || !a || !b || !out) return YAT_EINVAL;
+    hipLaunchKernelGGL(hadamard_scale_kernel, chunk_grid((int64_t)rows * (cols >> 3)), dim3(256), 0, (hipStream_t)stream, rows, cols,
+                       (const bf16_t*)a, lda, (const bf16_t*)b, ldb, scale, (bf16_t*)out, ldo);
     YAT_CHECK_LAUNCH();
     return YAT_OK;
 }
 
 int yat_hadamard_bwd(int rows, int cols, const void* dd, int ldd, const void* a1, int ld1, const void* a2, int ld2, float scale,
                      void* t1, int ldt1, void* t2, int ldt2, yat_stream_t stream) {
-    if (rows <= 0 || cols <= 0 || (cols & 7) || ((ldd | ld1 | ld2 | ldt1 | ldt2) & 7) || ldd < cols || ld1 < cols ||
-        ld2 < cols || ldt1 < cols || ldt2 < cols || !dd || !a1 || !a2 || !t1 || !t2)
-        return YAT_EINVAL;
-    const int64_t chunks = (int64_t)rows * (cols >> 3);
-    int64_t nb = (chunks + 255) / 256;
-    if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(hadamard_kernel<1>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, rows, cols, (const bf16_t*)dd,
-                       ldd, (const bf16_t*)a1, ld1, (const bf16_t*)a2, ld2, scale, (bf16_t*)t1, ldt1, (bf16_t*)t2, ldt2);
+    if (!views_ok(rows, cols, {ldd, ld1, ld2, ldt1, ldt2}) || !dd || !a1 || !a2 || !t1 || !t2) return YAT_EINVAL;
+    hipLaunchKernelGGL(hadamard_bwd_kernel, chunk_grid((int64_t)rows * (cols >> 3)), dim3(256), 0, (hipStream_t)stream, rows, cols,
+                       (const bf16_t*)dd, ldd, (const bf16_t*)a1, ld1, (const bf16_t*)a2, ld2, scale, (bf16_t*)t1, ldt1,
+                       (bf16_t*)t2, ldt2);
     YAT_CHECK_LAUNCH();
     return YAT_OK;
 }
 
-// DoRA: see dora_kernel above.  W, lw (= lora_B lora_A), delta / t1 are rows x cols bf16 views (cols % 8 == 0) with row strides
-// in elements; mag / dmag bf16 [rows]; s_buf / n_buf fp32 [rows] written by yat_dora_delta and read by yat_dora_bwd.
+// DoRA (the kernels' comment above).  W, lw (= lora_B lora_A), delta / t1 are rows x cols bf16 views (cols % 8 == 0) with row
+// strides in elements; mag / dmag bf16 [rows]; s_buf / n_buf fp32 [rows] written by yat_dora_delta and read by yat_dora_bwd.
 int yat_dora_delta(int rows, int cols, const void* W, int ldw, const void* lw, int ldl, const void* mag, float scaling,
                    void* delta, int ldd, float* s_buf, float* n_buf, yat_stream_t stream) {
-    if (rows <= 0 || cols <= 0 || (cols & 7) || ((ldw | ldl | ldd) & 7) || ldw < cols || ldl < cols || ldd < cols || !W || !lw ||
-        !mag || !delta || !s_buf || !n_buf)
-        return YAT_EINVAL;
-    hipLaunchKernelGGL(dora_kernel<0>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, cols, (const bf16_t*)W, ldw,
-                       (const bf16_t*)lw, ldl, (const bf16_t*)mag, scaling, (bf16_t*)delta, ldd, s_buf, n_buf,
-                       (const bf16_t*)nullptr, 0, (bf16_t*)nullptr);
+    if (!views_ok(rows, cols, {ldw, ldl, ldd}) || !W || !lw || !mag || !delta || !s_buf || !n_buf) return YAT_EINVAL;
+    hipLaunchKernelGGL(dora_delta_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, cols, (const bf16_t*)W, ldw,
+                       (const bf16_t*)lw, ldl, (const bf16_t*)mag, scaling, (bf16_t*)delta, ldd, s_buf, n_buf);
     YAT_CHECK_LAUNCH();
     return YAT_OK;
 }
 
 int yat_dora_bwd(int rows, int cols, const void* dd, int ldd, const void* W, int ldw, const void* lw, int ldl, float scaling,
                  const float* s_buf, const float* n_buf, void* t1, int ldt, void* dmag, yat_stream_t stream) {
-    if (rows <= 0 || cols <= 0 || (cols & 7) || ((ldw | ldl | ldd | ldt) & 7) || ldw < cols || ldl < cols || ldd < cols ||
-        ldt < cols || !W || !lw || !dd || !t1 || !dmag || !s_buf || !n_buf)
-        return YAT_EINVAL;
-    hipLaunchKernelGGL(dora_kernel<1>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, cols, (const bf16_t*)W, ldw,
-                       (const bf16_t*)lw, ldl, (const bf16_t*)nullptr, scaling, (bf16_t*)t1, ldt, (float*)s_buf, (float*)n_buf,
-                       (const bf16_t*)dd, ldd, (bf16_t*)dmag);
+    if (!views_ok(rows, cols, {ldw, ldl, ldd, ldt}) || !W || !lw || !dd || !t1 || !dmag || !s_buf || !n_buf) return YAT_EINVAL;
+    hipLaunchKernelGGL(dora_bwd_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, cols, (const bf16_t*)dd, ldd,
+                       (const bf16_t*)W, ldw, (const bf16_t*)lw, ldl, scaling, s_buf, n_buf, (bf16_t*)t1, ldt, (bf16_t*)dmag);
     YAT_CHECK_LAUNCH();
     return YAT_OK;
 }
