@@ -473,6 +473,19 @@ int yat_gradnorm_pieces_finish(int ntensor, const int* tensor_first_piece, const
 int yat_adamw_step(int64_t n, void* param, void* grad, void* exp_avg, void* exp_avg_sq, const float* clip_coef,
                    double lr, double beta1, double beta2, double eps, double weight_decay, int step, int zero_grad,
                    void* ema_shadow, double ema_decay, int background, yat_stream_t stream);
+/* The mixed-precision form of the same step: fp32 master weights, fp32 exp_avg / exp_avg_sq and an fp32 EMA shadow (or
+ * NULL); gradients stay bf16 and param_bf16 -- the buffer every forward and backward kernel reads -- is written in the same
+ * pass as bf16(master) (round to nearest even, NaN kept).  torch's single-tensor AdamW op sequence on fp32 tensors, no
+ * intermediate bf16 rounding: g' = float(g) * clip_coef[0] (when clip_coef != NULL; exact), p *= 1 - lr*wd (when wd != 0),
+ * m += (1-beta1)(g' - m), v = v*beta2 + (1-beta2) g' g', p += -(lr/bc1) m / (sqrt(v)/sqrt(bc2) + eps), then
+ * s -= (1-ema_decay)(s - p).  Scalars are prepared in double and narrowed to float as in yat_adamw_step.  28 B / parameter
+ * (36 with the shadow) against 14.  n % 8 == 0; every buffer 16-byte aligned.  YAT_EINVAL before any launch for n <= 0, n % 8,
+ * step < 1 or a NULL param_bf16 / master / grad_bf16 / exp_avg / exp_avg_sq.
+ * replaces: the same clip_grads + torch.optim.AdamW.step + EMAModel.step + zero_grad (common/trainer.py:246-248,347-356), had
+ * the reference kept its parameters, moments and shadow in fp32; an opt-in extension (yat_amd/optim.py master_weights). */
+int yat_adamw_master_step(int64_t n, void* param_bf16, float* master, void* grad_bf16, float* exp_avg, float* exp_avg_sq,
+                          const float* clip_coef, double lr, double beta1, double beta2, double eps, double weight_decay,
+                          int step, int zero_grad, float* ema_shadow, double ema_decay, yat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ *
  * DC-AE decoder (diffusers AutoencoderDC, decoder only): the VAE decode of the validation images,

@@ -188,6 +188,14 @@ def adapter_arithmetic(adapters):
     return "pre_add (peft order: base output, adapter output and their sum each rounded to bf16)"
 
 
+def optimizer_arithmetic(optimizer):
+    """One line for logs: which precision the optimizer state in force is kept and updated in (yat_amd/optim.py)."""
+    if getattr(optimizer, "master_weights", False):
+        return ("master_weights (fp32 master weights, moments and EMA shadow updated in fp32; the bf16 parameters are their "
+                "rounding; not the reference's arithmetic, fp32 state is not checkpointed)")
+    return "bf16 (parameters, moments and EMA shadow in bf16, rounded after every torch op: the reference's arithmetic)"
+
+
 @contextlib.contextmanager
 def _step_stream(dev):
     """Run the step loop on a stream of the compute-stream set (yat_amd/flat.py ``compute_stream``) instead of the default
@@ -348,8 +356,10 @@ class Model:
     def make_optimizer(self, trained):
         """:246-248 + :347-356 -- clip(1.0) + AdamW (+EMA) over the flat parameter buffer of a HIP model / adapter set."""
         p = self.params
+        # master_weights: the config key when present, else YAT_MASTER_WEIGHTS (FlatAdamW reads it for None)
         return FlatAdamW(trained, lr=p.learning_rate, weight_decay=p.weight_decay, max_grad_norm=1.0,
-                         use_ema=bool(getattr(p, "use_ema", False)), ema_decay=0.999, overlap_update=True)
+                         use_ema=bool(getattr(p, "use_ema", False)), ema_decay=0.999, overlap_update=True,
+                         master_weights=getattr(p, "master_weights", None))
 
     def make_sampler(self):
         """Cached-feature sampler over this rank's shard range (the intended path of :165-181); with ``compute_features: true``
@@ -429,9 +439,15 @@ class Model:
         # with adapters only they are trained (the base has no gradients, so AdamW leaves it alone in the reference too)
         trained = self.adapters if self.adapters is not None else self.model
         self.optimizer = self.make_optimizer(trained)
+        print(f"optimizer arithmetic: {optimizer_arithmetic(self.optimizer)}")
         if getattr(p, "shard_optimizer", False) and self.adapters is None:
             os.environ.setdefault("YAT_SHARD_OPTIMIZER", "1")       # (HipDDP reads it; an adapter set keeps the replicated step)
         self.accelerator.prepare(trained)
+        if getattr(self.optimizer, "master_weights", False):
+            # prepare() is the one writer of parameters after the optimizer exists: in a data-parallel job it broadcasts rank
+            # 0's flat_param (checkpoints and adapters are loaded before make_optimizer; the EMA swap of _validate_and_save
+            # restores bf16(master) exactly)
+            self.optimizer.resync_master()
         self.lr_scheduler = None
         if getattr(p, "warmup_steps", None) is not None:
             self.lr_scheduler = WarmupLR(self.optimizer, p.warmup_steps)

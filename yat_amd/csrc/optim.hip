@@ -234,6 +234,64 @@ __global__ __launch_bounds__(256, 10) void adamw_bg_kernel(int64_t nvec4, bf16_t
     }
 }
 
+// ---- mixed-precision step: fp32 master weights, fp32 moments, fp32 EMA shadow; bf16 gradients in, bf16 working copy out.
+// torch's single-tensor AdamW op sequence on fp32 tensors, i.e. the sequence of adamw_elem WITHOUT the bf16 roundings: a
+// parameter of magnitude 0.02 has a bf16 ulp of 6e-5, an update at the recipes' learning rates is ~1e-5, so the all-bf16 step
+// above leaves most weights where they are; the master copy takes every update and the working copy is its rounding.
+// Where torch's CPU kernels fuse a product into a sum (lerp_, and addcmul_ once the compiler contracts it) an fma stands.
+__device__ __forceinline__ void adamw_master_elem(float& pw, float g, float& m, float& v, float coef, bool clip, const AdamP& a) {
+    const float gr = clip ? g * coef : g;                           // grads.mul_(clip_coef_clamped): exact, g has 8 bits
+    if (a.use_wd) pw = pw * a.wd_mul;                               // param.mul_(1 - lr*wd)
+    m = __builtin_fmaf(a.w1, gr - m, m);                            // exp_avg.lerp_(grad, 1-beta1)
+    v = v * a.beta2;                                                // exp_avg_sq.mul_(beta2)
+    v = __builtin_fmaf(a.om_b2 * gr, gr, v);                        //   .addcmul_(grad, grad, value=1-beta2)
+    const float den = sqrtf(v) / a.bc2_sqrt + a.eps;                // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
+    pw = pw + a.neg_step_size * m / den;                            // param.addcdiv_(exp_avg, denom, value=-step_size)
+}
+
+__device__ __forceinline__ void load8f(const float* src, float* o) {
+    const f32x4 lo = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src));
+    const f32x4 hi = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src) + 1);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { o[e] = lo[e]; o[4 + e] = hi[e]; }
+}
+__device__ __forceinline__ void store8f(float* dst, const float* f) {
+    __builtin_nontemporal_store(f32x4{f[0], f[1], f[2], f[3]}, reinterpret_cast<f32x4*>(dst));
+    __builtin_nontemporal_store(f32x4{f[4], f[5], f[6], f[7]}, reinterpret_cast<f32x4*>(dst) + 1);
+}
+
+constexpr int MASTER_MAX_BLOCKS = 8192;      // x 256 lanes x 8 parameters = 2^24 parameters per grid pass (yat_amd/optim.py MASTER_GRID_PASS)
+
+// 8 parameters per thread and iteration, 16 bytes per access: 2 loads each of master, m, v (and the shadow) + 1 of the
+// gradients, all issued before the first use (7 or 9 independent loads in flight per lane); 28 B / parameter, 36 with EMA.
+// The fp32 state (19 - 26 GB at SANA-1.6B) streams through once per step: non-temporal, for the reason given at adamw_kernel.
+__global__ __launch_bounds__(256) void adamw_master_kernel(int64_t nvec, bf16_t* p, float* w, bf16_t* g, float* m, float* v,
+                                                           const float* clip_coef, float* ema, AdamP a) {
+    const bool clip = clip_coef != nullptr;
+    const float coef = clip ? clip_coef[0] : 1.0f;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+        float ww[8], gg[8], mm[8], vv[8], ss[8];
+        load8f(w + i * 8, ww);
+        load8f(m + i * 8, mm);
+        load8f(v + i * 8, vv);
+        const u32x4 rg = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(g + i * 8));
+        if (ema) load8f(ema + i * 8, ss);
+        unpack8(rg, gg);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            adamw_master_elem(ww[e], gg[e], mm[e], vv[e], coef, clip, a);
+            if (ema) ss[e] = ss[e] - a.ema_omd * (ss[e] - ww[e]);      // s.sub_(one_minus_decay * (s - p))
+        }
+        store8f(w + i * 8, ww);
+        store8f(m + i * 8, mm);
+        store8f(v + i * 8, vv);
+        if (ema) store8f(ema + i * 8, ss);
+        __builtin_nontemporal_store(pack8(ww), reinterpret_cast<u32x4*>(p + i * 8));   // the working copy: bf16(master), RNE, NaN kept
+        if (a.zero_grad) *reinterpret_cast<u32x4*>(g + i * 8) = u32x4{0u, 0u, 0u, 0u};
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -277,11 +335,9 @@ int yat_gradnorm_pieces_finish(int ntensor, const int* tensor_first_piece, const
     return YAT_OK;
 }
 
-int yat_adamw_step(int64_t n, void* param, void* grad, void* exp_avg, void* exp_avg_sq, const float* clip_coef, double lr,
-                   double beta1, double beta2, double eps, double weight_decay, int step, int zero_grad, void* ema_shadow,
-                   double ema_decay, int background, yat_stream_t stream) {
-    if (n <= 0 || (n & 7) || step < 1 || !param || !grad || !exp_avg || !exp_avg_sq) return YAT_EINVAL;
-    // scalar prep in double exactly as torch's python does, then narrowed to the kernels' opmath (float)
+// scalar prep in double exactly as torch's python does, then narrowed to the kernels' opmath (float)
+static AdamP adam_scalars(double lr, double beta1, double beta2, double eps, double weight_decay, int step, int zero_grad,
+                          double ema_decay) {
     const double dlr = lr, db1 = beta1, db2 = beta2;
     AdamP a;
     a.use_wd = weight_decay != 0.0;
@@ -295,6 +351,14 @@ int yat_adamw_step(int64_t n, void* param, void* grad, void* exp_avg, void* exp_
     a.eps = (float)eps;
     a.ema_omd = (float)(1.0 - ema_decay);
     a.zero_grad = zero_grad;
+    return a;
+}
+
+int yat_adamw_step(int64_t n, void* param, void* grad, void* exp_avg, void* exp_avg_sq, const float* clip_coef, double lr,
+                   double beta1, double beta2, double eps, double weight_decay, int step, int zero_grad, void* ema_shadow,
+                   double ema_decay, int background, yat_stream_t stream) {
+    if (n <= 0 || (n & 7) || step < 1 || !param || !grad || !exp_avg || !exp_avg_sq) return YAT_EINVAL;
+    const AdamP a = adam_scalars(lr, beta1, beta2, eps, weight_decay, step, zero_grad, ema_decay);
     if (background) {
         const int64_t nvec4 = n >> 2;
         int64_t nbg = (nvec4 + 255) / 256;
@@ -318,6 +382,20 @@ int yat_adamw_step(int64_t n, void* param, void* grad, void* exp_avg, void* exp_
     else if (variant == 3) YAT_ADAMW_LAUNCH(1, true);
     else YAT_ADAMW_LAUNCH(1, false);
 #undef YAT_ADAMW_LAUNCH
+    YAT_CHECK_LAUNCH();
+    return YAT_OK;
+}
+
+int yat_adamw_master_step(int64_t n, void* param_bf16, float* master, void* grad_bf16, float* exp_avg, float* exp_avg_sq,
+                          const float* clip_coef, double lr, double beta1, double beta2, double eps, double weight_decay,
+                          int step, int zero_grad, float* ema_shadow, double ema_decay, yat_stream_t stream) {
+    if (n <= 0 || (n & 7) || step < 1 || !param_bf16 || !master || !grad_bf16 || !exp_avg || !exp_avg_sq) return YAT_EINVAL;
+    const AdamP a = adam_scalars(lr, beta1, beta2, eps, weight_decay, step, zero_grad, ema_decay);
+    const int64_t nvec = n >> 3;
+    int64_t nb = (nvec + 255) / 256;
+    if (nb > MASTER_MAX_BLOCKS) nb = MASTER_MAX_BLOCKS;
+    hipLaunchKernelGGL(adamw_master_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, nvec, (bf16_t*)param_bf16,
+                       master, (bf16_t*)grad_bf16, exp_avg, exp_avg_sq, clip_coef, ema_shadow, a);
     YAT_CHECK_LAUNCH();
     return YAT_OK;
 }

@@ -849,6 +849,21 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, clip_coef, lr, beta1, beta2, ep
     _l.check(rc, "yat_adamw_step")
 
 
+def adamw_master_step(param, master, grad, exp_avg, exp_avg_sq, clip_coef, lr, beta1, beta2, eps, weight_decay, step,
+                      zero_grad=False, ema_shadow=None, ema_decay=0.0):
+    """fp32 ``master`` / ``exp_avg`` / ``exp_avg_sq`` / ``ema_shadow`` updated in fp32 from the bf16 ``grad``; ``param`` (bf16)
+    receives bf16(master).  include/yat_hip.h yat_adamw_master_step."""
+    _chk_bf16(param, grad)
+    f32 = (master, exp_avg, exp_avg_sq) + (() if ema_shadow is None else (ema_shadow,))
+    if any(t.dtype != torch.float32 or t.numel() != param.numel() or not t.is_contiguous() for t in f32) \
+            or grad.numel() != param.numel() or not (param.is_contiguous() and grad.is_contiguous()):
+        raise ValueError("adamw_master_step: fp32 contiguous master / moments / shadow of the parameters' size expected")
+    rc = _lib().yat_adamw_master_step(param.numel(), _p(param), _p(master), _p(grad), _p(exp_avg), _p(exp_avg_sq),
+                                      _p(clip_coef), lr, beta1, beta2, eps, weight_decay, step, int(zero_grad),
+                                      _p(ema_shadow), ema_decay, _stream())
+    _l.check(rc, "yat_adamw_master_step")
+
+
 # ----------------------------------------------------------------------------------------------- DC-AE decoder (yat_amd/dcae.py)
 def dcae_conv3x3(x, w, y, B, H, W, Cin, Cout, bias=None, upsample=False, silu=False, shortcut_mode=0, shortcut=None,
                  shortcut_channels=0, residual=None, out_nchw=False):

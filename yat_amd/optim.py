@@ -11,6 +11,14 @@ parameters (1 / N of the AdamW traffic) and the buckets' parameters come back by
 forward.  The update is elementwise and the gradient norm is computed over PIECES -- tensors cut at the eighths of their
 bucket, ``norm_pieces`` -- whose sums do not depend on who computed them, so the sharded step is BIT-IDENTICAL to the
 replicated one (same reduced gradients in, same parameters out) for N in {1, 2, 4, 8}.
+
+Master weights (``FlatAdamW(master_weights=True)``, ``YAT_MASTER_WEIGHTS=1``, config key ``master_weights``; off by default):
+an extension of this package, not a restatement of the reference.  At the recipes' learning rates (1e-6 ... 2e-5) an AdamW
+update is a fraction of a bf16 ulp of most weights, so the all-bf16 step above leaves them bitwise where they were.  With
+master weights the step keeps an fp32 copy of every trained parameter, fp32 moments and an fp32 EMA shadow (12 B / parameter
+more, 16 with EMA) and yat_adamw_master_step writes the bf16 flat buffer -- still what every forward and backward kernel
+reads -- as bf16(master).  Gradients, the gradient norm and the clip coefficient stay exactly as they are.  The fp32 state is
+not checkpointed: a restarted run re-derives its master from the bf16 weights it loads.  The sharded step is refused.
 """
 from __future__ import annotations
 
@@ -25,6 +33,13 @@ BF16 = torch.bfloat16
 
 NORM_CHUNK = 1 << 18        # elements per partial sum of the gradient norm (csrc/optim.hip NORM_CHUNK)
 NORM_PARTS = 8              # a bucket's pieces never straddle an eighth of it: shards of 1, 2, 4 or 8 ranks own whole pieces
+MASTER_GRID_PASS = 8192 * 256 * 8   # parameters one pass of yat_adamw_master_step's capped grid covers (csrc/optim.hip MASTER_MAX_BLOCKS)
+_OFF = ("", "0", "false", "no", "off")
+
+
+def master_weights_default():
+    """``YAT_MASTER_WEIGHTS``: what ``FlatAdamW(master_weights=None)`` does (unset / 0 / false / no / off = the bf16 step)."""
+    return os.environ.get("YAT_MASTER_WEIGHTS", "").strip().lower() not in _OFF
 
 
 def norm_pieces(seg_start, bucket_bounds, parts=NORM_PARTS):
@@ -68,13 +83,17 @@ def norm_pieces(seg_start, bucket_bounds, parts=NORM_PARTS):
 
 class FlatAdamW:
     def __init__(self, model, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0, use_ema=False,
-                 ema_decay=0.999, overlap_update=False):
+                 ema_decay=0.999, overlap_update=False, master_weights=None):
         self.model = model
         dev = model.flat_param.device
         self.param_groups = [dict(lr=lr, initial_lr=lr, weight_decay=weight_decay, betas=betas, eps=eps)]
         self.max_grad_norm = max_grad_norm
-        self.exp_avg = torch.zeros_like(model.flat_param)
-        self.exp_avg_sq = torch.zeros_like(model.flat_param)
+        # master_weights: fp32 master copy, moments and shadow; model.flat_param becomes the working copy bf16(master)
+        self.master_weights = master_weights_default() if master_weights is None else bool(master_weights)
+        self.master = model.flat_param.float() if self.master_weights else None
+        state_dtype = torch.float32 if self.master_weights else model.flat_param.dtype
+        self.exp_avg = torch.zeros_like(model.flat_param, dtype=state_dtype)
+        self.exp_avg_sq = torch.zeros_like(model.flat_param, dtype=state_dtype)
         self.step_count = 0
         self.seg_start = model.seg_start.to(dev)
         # gradient norm over pieces (tensors cut at the eighths of their bucket): the sums a sharded step can split over ranks
@@ -86,7 +105,7 @@ class FlatAdamW:
         self._owned, self._owned_for = None, None
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
         self.clip_coef = torch.ones(1, dtype=torch.float32, device=dev)
-        self.ema_shadow = model.flat_param.clone() if use_ema else None
+        self.ema_shadow = (self.master if self.master_weights else model.flat_param).clone() if use_ema else None
         self.ema_decay = ema_decay
         self.ema_steps = 0
         # overlap_update: the update runs bucket by bucket (forward order) on its own stream and hands the model one
@@ -105,12 +124,22 @@ class FlatAdamW:
             return 0.0
         return max(min((1 + step) / (10 + step), self.ema_decay), 0.0)
 
+    def resync_master(self):
+        """Re-read the fp32 master from the bf16 flat buffer: for whoever writes parameters (a load) after this optimizer was
+        built -- the step itself only ever writes ``flat_param`` as bf16(master).  Nothing to do without master weights."""
+        if self.master is not None:
+            self.model.join_pending_update()
+            self.master.copy_(self.model.flat_param)
+
     def step(self):
         g = self.param_groups[0]
-        self.step_count += 1
         m = self.model
-        coef = None
         shard = self._shard()
+        if shard is not None and self.master_weights:
+            raise NotImplementedError("master_weights with a sharded optimizer step (shard_optimizer / YAT_SHARD_OPTIMIZER) "
+                                      "is not built: use the replicated step or the bf16 optimizer state")
+        self.step_count += 1
+        coef = None
         if self.max_grad_norm is not None:
             ops.gradnorm_pieces_partial(m.flat_grad, self._piece_start, self._chunk_base, self._max_chunks,
                                         None if shard is None else self._owned_mask(shard), self._partial)
@@ -130,6 +159,13 @@ class FlatAdamW:
         def update(lo, hi, step_count=None):
             # no gradient clear: every backward overwrites the whole flat gradient (accumulate_grads=False on the
             # first micro-step), like the reference's zero_grad(set_to_none=True) which writes nothing either
+            if self.master_weights:
+                ops.adamw_master_step(m.flat_param[lo:hi], self.master[lo:hi], m.flat_grad[lo:hi], self.exp_avg[lo:hi],
+                                      self.exp_avg_sq[lo:hi], coef, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
+                                      g["weight_decay"], self.step_count if step_count is None else step_count,
+                                      zero_grad=False, ema_shadow=None if self.ema_shadow is None else self.ema_shadow[lo:hi],
+                                      ema_decay=ema_decay)
+                return
             ops.adamw_step(m.flat_param[lo:hi], m.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], coef,
                            g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
                            self.step_count if step_count is None else step_count,
