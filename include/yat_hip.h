@@ -486,6 +486,27 @@ int yat_adamw_step(int64_t n, void* param, void* grad, void* exp_avg, void* exp_
 int yat_adamw_master_step(int64_t n, void* param_bf16, float* master, void* grad_bf16, float* exp_avg, float* exp_avg_sq,
                           const float* clip_coef, double lr, double beta1, double beta2, double eps, double weight_decay,
                           int step, int zero_grad, float* ema_shadow, double ema_decay, yat_stream_t stream);
+/* The stochastic-rounding form of the same step: ALL five buffers bf16 (ema_shadow or NULL), 14 B / parameter (18 with the
+ * shadow) and no extra state.  The arithmetic is yat_adamw_master_step's fp32 sequence applied to the values unpacked from
+ * bf16 (g * clip_coef[0] unrounded, no intermediate bf16 rounding); param, exp_avg, exp_avg_sq and the shadow are each stored
+ * through sr_bf16(x, r): finite x -> the top 16 bits of (bits(x) + r) for a 16-bit random r (32-bit add, then truncation: away
+ * from zero with probability (low 16 bits of x) / 65536, a bf16-representable x unchanged, +-0 kept); NaN / +-Inf -> the
+ * round-to-nearest conversion.  The shadow is s - (1-ema_decay)(s - p_stored) with p_stored the bf16 parameter just written.
+ * Random bits: Philox4x32 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85; the round count is
+ * SR_PHILOX_ROUNDS in csrc/optim.hip), one call per pair of consecutive parameters: with idx = elem_offset + i for position i of
+ * this call and j = idx >> 1, key = (seed lo, seed hi), counter = (j lo, j hi, rng_step lo, rng_step hi); the even parameter
+ * of the pair takes output words (w0, w1), the odd one (w2, w3); of a parameter's two words (wa, wb): param <- wa & 0xFFFF,
+ * exp_avg <- wa >> 16, exp_avg_sq <- wb & 0xFFFF, ema_shadow <- wb >> 16.  The result therefore depends on (seed, rng_step,
+ * global index) only: a buffer may be updated in any number of calls over slices (elem_offset = the slice's offset in the whole
+ * buffer), by any rank, with the same bits.  `step` is AdamW's bias-correction step, rng_step the caller's own step counter.
+ * n % 8 == 0, elem_offset % 8 == 0; every buffer 16-byte aligned.  YAT_EINVAL before any launch for n <= 0, n % 8,
+ * elem_offset < 0, elem_offset % 8, rng_step < 0, step < 1 or a NULL param / grad / exp_avg / exp_avg_sq.
+ * replaces: the same clip_grads + torch.optim.AdamW.step + EMAModel.step + zero_grad (common/trainer.py:246-248,347-356) with
+ * the reference's bf16 state but not its arithmetic; an opt-in extension (yat_amd/optim.py stochastic_rounding). */
+int yat_adamw_sr_step(int64_t n, void* param, void* grad, void* exp_avg, void* exp_avg_sq, const float* clip_coef,
+                      double lr, double beta1, double beta2, double eps, double weight_decay, int step, int zero_grad,
+                      void* ema_shadow, double ema_decay, uint64_t seed, int64_t rng_step, int64_t elem_offset,
+                      yat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ *
  * DC-AE decoder (diffusers AutoencoderDC, decoder only): the VAE decode of the validation images,

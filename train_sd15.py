@@ -68,10 +68,11 @@ class SD15Model(Model):
         self.pipe = None
 
     def make_optimizer(self, trained):
-        from yat_amd.optim import master_weights_default
-        key = getattr(self.params, "master_weights", None)             # the config key, else YAT_MASTER_WEIGHTS
-        if key or (key is None and master_weights_default()):
-            print("master_weights is ignored: this recipe runs torch's own AdamW on the host, in the parameters' dtype")
+        from yat_amd.optim import master_weights_default, stochastic_rounding_default
+        for name, default in (("master_weights", master_weights_default), ("stochastic_rounding", stochastic_rounding_default)):
+            key = getattr(self.params, name, None)                     # the config key, else YAT_MASTER_WEIGHTS / YAT_STOCHASTIC_ROUNDING
+            if key or (key is None and default()):
+                print(f"{name} is ignored: this recipe runs torch's own AdamW on the host, in the parameters' dtype")
         return _TorchClipAdamW(trained, self.params.learning_rate, self.params.weight_decay)
 
     def extract_latents(self, images):

@@ -193,6 +193,9 @@ def optimizer_arithmetic(optimizer):
     if getattr(optimizer, "master_weights", False):
         return ("master_weights (fp32 master weights, moments and EMA shadow updated in fp32; the bf16 parameters are their "
                 "rounding; not the reference's arithmetic, fp32 state is not checkpointed)")
+    if getattr(optimizer, "stochastic_rounding", False):
+        return ("stochastic_rounding (parameters, moments and EMA shadow in bf16; the update is computed in fp32 from the bf16 "
+                "state and every stored value is Philox-rounded up or down, unbiased; not the reference's arithmetic)")
     return "bf16 (parameters, moments and EMA shadow in bf16, rounded after every torch op: the reference's arithmetic)"
 
 
@@ -356,10 +359,13 @@ class Model:
     def make_optimizer(self, trained):
         """:246-248 + :347-356 -- clip(1.0) + AdamW (+EMA) over the flat parameter buffer of a HIP model / adapter set."""
         p = self.params
-        # master_weights: the config key when present, else YAT_MASTER_WEIGHTS (FlatAdamW reads it for None)
+        # master_weights / stochastic_rounding: the config key when present, else YAT_MASTER_WEIGHTS / YAT_STOCHASTIC_ROUNDING
+        # (FlatAdamW reads them for None); the rounding seed is the dataset seed, the same on every rank
         return FlatAdamW(trained, lr=p.learning_rate, weight_decay=p.weight_decay, max_grad_norm=1.0,
                          use_ema=bool(getattr(p, "use_ema", False)), ema_decay=0.999, overlap_update=True,
-                         master_weights=getattr(p, "master_weights", None))
+                         master_weights=getattr(p, "master_weights", None),
+                         stochastic_rounding=getattr(p, "stochastic_rounding", None),
+                         sr_seed=int(getattr(p, "dataset_seed", 0) or 0))
 
     def make_sampler(self):
         """Cached-feature sampler over this rank's shard range (the intended path of :165-181); with ``compute_features: true``

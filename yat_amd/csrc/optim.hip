@@ -292,6 +292,92 @@ __global__ __launch_bounds__(256) void adamw_master_kernel(int64_t nvec, bf16_t*
     }
 }
 
+// ---- stochastic-rounding step: ALL state bf16 (p, g, m, v, shadow), the update computed in fp32 from it (adamw_master_elem's
+// sequence on the unpacked values) and every stored value rounded up or down at random, so that E[stored] = computed: a
+// sub-ulp update, the 1e-3 decay of v and of the shadow accumulate in expectation where round-to-nearest drops them.
+// 14 B / parameter (18 with the shadow) like adamw_kernel, no extra state; the random bits are made in registers.
+//   sr_bf16(x, r), r a 16-bit random: finite x -> the top 16 bits of (bits(x) + r), a 32-bit add then truncation, i.e. away
+//   from zero with probability (low 16 bits of x) / 65536, a bf16-representable x unchanged for every r; NaN and +-Inf take
+//   the round-to-nearest conversion of pack8 (the add must not touch them: a NaN payload + r can carry into the sign).
+//   bits: Philox4x32 (multipliers D2511F53 / CD9E8D57, Weyl key increments 9E3779B9 / BB67AE85), one call per PAIR of
+//   consecutive parameters: pair j = (elem_offset + i) >> 1, key = (seed lo, seed hi), counter = (j lo, j hi, rng_step lo,
+//   rng_step hi); the even parameter takes the words (w0, w1), the odd one (w2, w3); of a parameter's words (wa, wb):
+//   p <- wa & 0xFFFF, exp_avg <- wa >> 16, exp_avg_sq <- wb & 0xFFFF, shadow <- wb >> 16.
+// The bits depend on (seed, rng_step, global index, field) only: not on the grid, not on how the buffer is sliced into calls
+// (buckets, ranges, rank shards), not on which rank runs the call.
+constexpr int SR_PHILOX_ROUNDS = 10;         // tests/sr_adamw_ref.py PHILOX_ROUNDS restates this; the two must agree
+
+__device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                           uint32_t* w) {
+#pragma unroll
+    for (int r = 0; r < SR_PHILOX_ROUNDS; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;    // v_mad_u64_u32: high and low at once
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+
+__device__ __forceinline__ uint32_t sr_bf16(float x, uint32_t r) {          // r < 65536; the bf16 in the low half
+    const uint32_t u = __float_as_uint(x);
+    return (u & 0x7f800000u) != 0x7f800000u ? (u + r) >> 16 : (uint32_t)f2bf(x);
+}
+
+// adamw_kernel<1, true>'s shape: 8 parameters per lane and iteration, the four (five) 16-byte loads issued before the first
+// use, non-temporal, grid capped at MASTER_MAX_BLOCKS with a grid-stride loop; four Philox calls per 8-parameter vector.
+__global__ __launch_bounds__(256) void adamw_sr_kernel(int64_t nvec, bf16_t* p, bf16_t* g, bf16_t* m, bf16_t* v,
+                                                       const float* clip_coef, bf16_t* ema, AdamP a, uint32_t seed_lo,
+                                                       uint32_t seed_hi, uint32_t step_lo, uint32_t step_hi, int64_t pair0) {
+    const bool clip = clip_coef != nullptr;
+    const float coef = clip ? clip_coef[0] : 1.0f;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+        const u32x4 rp = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + i * 8));
+        const u32x4 rg = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(g + i * 8));
+        const u32x4 rm = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(m + i * 8));
+        const u32x4 rv = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(v + i * 8));
+        u32x4 rs = u32x4{0u, 0u, 0u, 0u};
+        if (ema) rs = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(ema + i * 8));
+        const uint64_t j0 = (uint64_t)(pair0 + i * 4);         // elem_offset % 8 == 0: the vector's four pairs are j0 .. j0 + 3
+        float pp[8], gg[8], mm[8], vv[8], ss[8];
+        unpack8(rp, pp);
+        unpack8(rg, gg);
+        unpack8(rm, mm);
+        unpack8(rv, vv);
+        unpack8(rs, ss);
+        u32x4 op, om, ov, os;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            uint32_t w[4];
+            philox4x32((uint32_t)j0 | q, (uint32_t)(j0 >> 32), step_lo, step_hi, seed_lo, seed_hi, w);
+            uint32_t hp[2], hm[2], hv[2], hs[2] = {0u, 0u};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int e = 2 * q + h;
+                const uint32_t wa = w[2 * h], wb = w[2 * h + 1];
+                adamw_master_elem(pp[e], gg[e], mm[e], vv[e], coef, clip, a);
+                hp[h] = sr_bf16(pp[e], wa & 0xffffu);
+                hm[h] = sr_bf16(mm[e], wa >> 16);
+                hv[h] = sr_bf16(vv[e], wb & 0xffffu);
+                if (ema) {                                      // the EMA of the weights the model uses: the bf16 just stored
+                    const float ps = __uint_as_float(hp[h] << 16);
+                    hs[h] = sr_bf16(ss[e] - a.ema_omd * (ss[e] - ps), wb >> 16);
+                }
+            }
+            op[q] = hp[0] | (hp[1] << 16);
+            om[q] = hm[0] | (hm[1] << 16);
+            ov[q] = hv[0] | (hv[1] << 16);
+            os[q] = hs[0] | (hs[1] << 16);
+        }
+        __builtin_nontemporal_store(op, reinterpret_cast<u32x4*>(p + i * 8));
+        __builtin_nontemporal_store(om, reinterpret_cast<u32x4*>(m + i * 8));
+        __builtin_nontemporal_store(ov, reinterpret_cast<u32x4*>(v + i * 8));
+        if (ema) __builtin_nontemporal_store(os, reinterpret_cast<u32x4*>(ema + i * 8));
+        if (a.zero_grad) *reinterpret_cast<u32x4*>(g + i * 8) = u32x4{0u, 0u, 0u, 0u};
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -396,6 +482,23 @@ int yat_adamw_master_step(int64_t n, void* param_bf16, float* master, void* grad
     if (nb > MASTER_MAX_BLOCKS) nb = MASTER_MAX_BLOCKS;
     hipLaunchKernelGGL(adamw_master_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, nvec, (bf16_t*)param_bf16,
                        master, (bf16_t*)grad_bf16, exp_avg, exp_avg_sq, clip_coef, ema_shadow, a);
+    YAT_CHECK_LAUNCH();
+    return YAT_OK;
+}
+
+int yat_adamw_sr_step(int64_t n, void* param, void* grad, void* exp_avg, void* exp_avg_sq, const float* clip_coef, double lr,
+                      double beta1, double beta2, double eps, double weight_decay, int step, int zero_grad, void* ema_shadow,
+                      double ema_decay, uint64_t seed, int64_t rng_step, int64_t elem_offset, yat_stream_t stream) {
+    if (n <= 0 || (n & 7) || elem_offset < 0 || (elem_offset & 7) || rng_step < 0 || step < 1 || !param || !grad || !exp_avg ||
+        !exp_avg_sq)
+        return YAT_EINVAL;
+    const AdamP a = adam_scalars(lr, beta1, beta2, eps, weight_decay, step, zero_grad, ema_decay);
+    const int64_t nvec = n >> 3;
+    int64_t nb = (nvec + 255) / 256;
+    if (nb > MASTER_MAX_BLOCKS) nb = MASTER_MAX_BLOCKS;
+    hipLaunchKernelGGL(adamw_sr_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, nvec, (bf16_t*)param,
+                       (bf16_t*)grad, (bf16_t*)exp_avg, (bf16_t*)exp_avg_sq, clip_coef, (bf16_t*)ema_shadow, a, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), (uint32_t)rng_step, (uint32_t)((uint64_t)rng_step >> 32), elem_offset >> 1);
     YAT_CHECK_LAUNCH();
     return YAT_OK;
 }

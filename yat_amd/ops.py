@@ -864,6 +864,20 @@ def adamw_master_step(param, master, grad, exp_avg, exp_avg_sq, clip_coef, lr, b
     _l.check(rc, "yat_adamw_master_step")
 
 
+def adamw_sr_step(param, grad, exp_avg, exp_avg_sq, clip_coef, lr, beta1, beta2, eps, weight_decay, step, zero_grad=False,
+                  ema_shadow=None, ema_decay=0.0, seed=0, rng_step=0, elem_offset=0):
+    """All-bf16 state updated in fp32 and stored with Philox stochastic rounding; ``elem_offset``: where ``param`` starts in the
+    whole buffer (the random bits follow the global index).  include/yat_hip.h yat_adamw_sr_step."""
+    bf = (param, grad, exp_avg, exp_avg_sq) + (() if ema_shadow is None else (ema_shadow,))
+    _chk_bf16(*bf)
+    if any(t.numel() != param.numel() or not t.is_contiguous() for t in bf):
+        raise ValueError("adamw_sr_step: bf16 contiguous gradients / moments / shadow of the parameters' size expected")
+    rc = _lib().yat_adamw_sr_step(param.numel(), _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), _p(clip_coef), lr, beta1,
+                                  beta2, eps, weight_decay, step, int(zero_grad), _p(ema_shadow), ema_decay,
+                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(rng_step), int(elem_offset), _stream())
+    _l.check(rc, "yat_adamw_sr_step")
+
+
 # ----------------------------------------------------------------------------------------------- DC-AE decoder (yat_amd/dcae.py)
 def dcae_conv3x3(x, w, y, B, H, W, Cin, Cout, bias=None, upsample=False, silu=False, shortcut_mode=0, shortcut=None,
                  shortcut_channels=0, residual=None, out_nchw=False):

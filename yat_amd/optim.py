@@ -19,6 +19,16 @@ master weights the step keeps an fp32 copy of every trained parameter, fp32 mome
 more, 16 with EMA) and yat_adamw_master_step writes the bf16 flat buffer -- still what every forward and backward kernel
 reads -- as bf16(master).  Gradients, the gradient norm and the clip coefficient stay exactly as they are.  The fp32 state is
 not checkpointed: a restarted run re-derives its master from the bf16 weights it loads.  The sharded step is refused.
+
+Stochastic rounding (``FlatAdamW(stochastic_rounding=True, sr_seed=...)``, ``YAT_STOCHASTIC_ROUNDING=1``, config key
+``stochastic_rounding``; off by default, and refused together with master weights): the other answer to the same stall, also an
+extension.  The state stays bf16 -- no master copy, no extra bytes, nothing more to checkpoint -- and yat_adamw_sr_step computes
+the update in fp32 from it and rounds every stored parameter, moment and shadow value up or down with the probability of its
+fractional position between the two bf16 neighbours, so the stored value is unbiased: sub-ulp updates, the 1e-3 decay of
+``exp_avg_sq`` and the shadow's 1e-3 pull accumulate in expectation.  The random bits are Philox4x32 of (``sr_seed``, the
+optimizer's step count, the parameter's index in the flat buffer, the field) and of nothing else: every way this class slices
+the buffer into calls -- buckets under ``overlap_update``, ``update_ranges``, rank shards -- gives the same bits, data-parallel
+replicas stay identical and the sharded step stays bit-identical to the replicated one.
 """
 from __future__ import annotations
 
@@ -40,6 +50,11 @@ _OFF = ("", "0", "false", "no", "off")
 def master_weights_default():
     """``YAT_MASTER_WEIGHTS``: what ``FlatAdamW(master_weights=None)`` does (unset / 0 / false / no / off = the bf16 step)."""
     return os.environ.get("YAT_MASTER_WEIGHTS", "").strip().lower() not in _OFF
+
+
+def stochastic_rounding_default():
+    """``YAT_STOCHASTIC_ROUNDING``: what ``FlatAdamW(stochastic_rounding=None)`` does (unset / 0 / false / no / off = round to nearest)."""
+    return os.environ.get("YAT_STOCHASTIC_ROUNDING", "").strip().lower() not in _OFF
 
 
 def norm_pieces(seg_start, bucket_bounds, parts=NORM_PARTS):
@@ -83,13 +98,19 @@ def norm_pieces(seg_start, bucket_bounds, parts=NORM_PARTS):
 
 class FlatAdamW:
     def __init__(self, model, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0, use_ema=False,
-                 ema_decay=0.999, overlap_update=False, master_weights=None):
+                 ema_decay=0.999, overlap_update=False, master_weights=None, stochastic_rounding=None, sr_seed=0):
         self.model = model
         dev = model.flat_param.device
         self.param_groups = [dict(lr=lr, initial_lr=lr, weight_decay=weight_decay, betas=betas, eps=eps)]
         self.max_grad_norm = max_grad_norm
         # master_weights: fp32 master copy, moments and shadow; model.flat_param becomes the working copy bf16(master)
         self.master_weights = master_weights_default() if master_weights is None else bool(master_weights)
+        # stochastic_rounding: bf16 state, fp32 update, Philox-rounded stores (yat_adamw_sr_step); sr_seed is the same on every rank
+        self.stochastic_rounding = stochastic_rounding_default() if stochastic_rounding is None else bool(stochastic_rounding)
+        if self.master_weights and self.stochastic_rounding:
+            raise ValueError("master_weights and stochastic_rounding are two answers to the same stall: choose one "
+                             "(arguments, config keys or YAT_MASTER_WEIGHTS / YAT_STOCHASTIC_ROUNDING)")
+        self.sr_seed = int(sr_seed)
         self.master = model.flat_param.float() if self.master_weights else None
         state_dtype = torch.float32 if self.master_weights else model.flat_param.dtype
         self.exp_avg = torch.zeros_like(model.flat_param, dtype=state_dtype)
@@ -165,6 +186,15 @@ class FlatAdamW:
                                       g["weight_decay"], self.step_count if step_count is None else step_count,
                                       zero_grad=False, ema_shadow=None if self.ema_shadow is None else self.ema_shadow[lo:hi],
                                       ema_decay=ema_decay)
+                return
+            if self.stochastic_rounding:
+                # rng_step is the optimizer's own counter (a range's bias-correction step may repeat across steps); the bits
+                # follow the global index lo + i, so any slicing of the buffer into calls gives the same result
+                ops.adamw_sr_step(m.flat_param[lo:hi], m.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], coef,
+                                  g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
+                                  self.step_count if step_count is None else step_count, zero_grad=False,
+                                  ema_shadow=None if self.ema_shadow is None else self.ema_shadow[lo:hi], ema_decay=ema_decay,
+                                  seed=self.sr_seed, rng_step=self.step_count, elem_offset=lo)
                 return
             ops.adamw_step(m.flat_param[lo:hi], m.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], coef,
                            g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
