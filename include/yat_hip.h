@@ -338,7 +338,9 @@ int yat_lokr_small_wgrad(int64_t rows, int R, int N, int r_out, const void* a, c
                          float scale, int accumulate, void* workspace, yat_stream_t stream);
 
 /* elementwise helpers: y = act(x) and dx = dy * act'(x) on bf16 (time-embed / caption MLPs);
- * act: 1 SiLU, 2 GELU(tanh).  add: out = bf16(a + b).  f32->bf16 convert. */
+ * act: 1 SiLU, 2 GELU(tanh).  add: out = bf16(a + b).  f32->bf16 convert (round to nearest even, NaN stays NaN).
+ * Every finite x gives a finite y; dx / dy is finite for every finite x too, except GELU(tanh)' for x >= 4.07e19, which
+ * is NaN as torch's own fp32 backward is there (the GEMM epilogues evaluate the same functions). */
 int yat_act_fwd(int64_t n, int act, const void* x, void* y, yat_stream_t stream);
 int yat_act_bwd(int64_t n, int act, const void* x, const void* dy, void* dx, yat_stream_t stream);
 int yat_add_bf16(int64_t n, const void* a, const void* b, void* out, yat_stream_t stream);

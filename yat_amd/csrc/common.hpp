@@ -105,7 +105,10 @@ __device__ __forceinline__ float gelu_tanh_f(float x) { return x * gelu_gate_f(x
 __device__ __forceinline__ float dgelu_tanh_f(float x) {
     const float k0x2 = 2.0f * 0.7978845608028654f, k1x3 = 3.0f * 0.044715f;
     const float s = gelu_gate_f(x);
-    return s * __builtin_fmaf(x * (1.0f - s), k0x2 * __builtin_fmaf(k1x3 * x, x, 1.0f), 1.0f);
+    // x <= -1.17e13: x (1 - s) u' overflows to -inf where s = 0, and 0 * -inf is NaN; the largest finite float gives the
+    // derivative's -0 there (a select, not fmaxf: the NaN of a NaN input, and of 0 * inf beyond 4e19, stays)
+    const float t = __builtin_fmaf(x * (1.0f - s), k0x2 * __builtin_fmaf(k1x3 * x, x, 1.0f), 1.0f);
+    return s * (t == -__builtin_inff() ? -3.402823466e+38f : t);
 }
 
 // Workgroups are dealt round-robin to the 8 XCDs (private L2 each) by their linear index (x fastest).  This maps the

@@ -116,6 +116,21 @@ def _chk_bf16(*ts):
             raise TypeError(f"expected bf16, got {t.dtype}")
 
 
+def _chk_dense(op, dtype, n=None, **ts):
+    """Argument check of the wrappers that hand the library an element count and raw pointers: every tensor (None =
+    an absent optional operand) has ``dtype``, is contiguous and, with ``n``, holds exactly ``n`` elements.  Raises
+    ValueError before any library call -- the kernels would read a strided view as dense, or past a shorter operand."""
+    for name, t in ts.items():
+        if t is None:
+            continue
+        if t.dtype != dtype:
+            raise ValueError(f"{op}: {name} must be {dtype}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{op}: {name} must be contiguous")
+        if n is not None and t.numel() != n:
+            raise ValueError(f"{op}: {name} has {t.numel()} elements, expected {n}")
+
+
 # ----------------------------------------------------------------------------------------------- GEMM
 GEMM_STREAMS = 1
 
@@ -677,12 +692,14 @@ def dwconv_glu_bwd(s, z, B, h, w, Hc, wdw, bdw, dy, dz, dwdw, dbdw, workspace, a
 
 # ----------------------------------------------------------------------------------------------- elementwise / recipe
 def act_fwd(x, act, y=None):
+    _chk_dense("act_fwd", BF16, x.numel(), x=x, y=y)
     y = y if y is not None else torch.empty_like(x)
     _l.check(_lib().yat_act_fwd(x.numel(), ACT[act], _p(x), _p(y), _stream()), "yat_act_fwd")
     return y
 
 
 def act_bwd(x, dy, act, dx=None):
+    _chk_dense("act_bwd", BF16, x.numel(), x=x, dy=dy, dx=dx)
     dx = dx if dx is not None else torch.empty_like(x)
     rc = _lib().yat_act_bwd(x.numel(), ACT[act], _p(x), _p(dy), _p(dx), _stream())
     if TEXT_ROWS is not None:
@@ -713,12 +730,15 @@ def zero_last_rows(x2d, n):
 
 
 def add_bf16(a, b, out=None):
+    _chk_dense("add_bf16", BF16, a.numel(), a=a, b=b, out=out)
     out = out if out is not None else torch.empty_like(a)
     _l.check(_lib().yat_add_bf16(a.numel(), _p(a), _p(b), _p(out), _stream()), "yat_add_bf16")
     return out
 
 
 def f32_to_bf16(x, y=None):
+    _chk_dense("f32_to_bf16", torch.float32, x=x)
+    _chk_dense("f32_to_bf16", BF16, x.numel(), y=y)
     y = y if y is not None else torch.empty(x.shape, dtype=BF16, device=x.device)
     _l.check(_lib().yat_f32_to_bf16(x.numel(), _p(x), _p(y), _stream()), "yat_f32_to_bf16")
     return y
@@ -726,6 +746,9 @@ def f32_to_bf16(x, y=None):
 
 def transpose(x3d, out=None):
     """yat_transpose_bf16: [B, R, C] -> [B, C, R]."""
+    if x3d.dim() != 3:
+        raise ValueError("transpose: x3d must be [B, R, C]")
+    _chk_dense("transpose", BF16, x3d.numel(), x3d=x3d, out=out)
     B, R, Cc = x3d.shape
     out = out if out is not None else torch.empty(B, Cc, R, dtype=BF16, device=x3d.device)
     _l.check(_lib().yat_transpose_bf16(B, R, Cc, _p(x3d), _p(out), _stream()), "yat_transpose_bf16")
@@ -734,12 +757,26 @@ def transpose(x3d, out=None):
 
 def timestep_embed(t_f32, dim=256, out=None):
     B = t_f32.numel()
+    _chk_dense("timestep_embed", torch.float32, t_f32=t_f32)
+    _chk_dense("timestep_embed", BF16, B * dim, out=out)
     out = out if out is not None else torch.empty(B, dim, dtype=BF16, device=t_f32.device)
     _l.check(_lib().yat_timestep_embed_fwd(B, dim, _p(t_f32), _p(out), _stream()), "yat_timestep_embed_fwd")
     return out
 
 
+def _chk_text_rows(op, src_cat, offsets_i32, B, T, Cdim, dst, dst_numel, mask_i64, key_bias_f32, kv_len_i32):
+    _chk_dense(op, BF16, src_cat=src_cat)
+    _chk_dense(op, BF16, dst_numel, dst=dst)
+    _chk_dense(op, torch.int32, offsets_i32=offsets_i32)
+    _chk_dense(op, torch.int64, B * T, mask_i64=mask_i64)
+    _chk_dense(op, torch.float32, B * T, key_bias_f32=key_bias_f32)
+    _chk_dense(op, torch.int32, B, kv_len_i32=kv_len_i32)
+    if offsets_i32.numel() < B + 1 or src_cat.numel() % Cdim:
+        raise ValueError(f"{op}: offsets need B + 1 entries and the source whole rows of {Cdim} elements")
+
+
 def pad_mask(src_cat, offsets_i32, B, T, Cdim, dst, mask_i64, key_bias_f32, kv_len_i32):
+    _chk_text_rows("pad_mask", src_cat, offsets_i32, B, T, Cdim, dst, B * T * Cdim, mask_i64, key_bias_f32, kv_len_i32)
     rc = _lib().yat_pad_mask(B, T, Cdim, _p(src_cat), _p(offsets_i32), _p(dst), _p(mask_i64), _p(key_bias_f32),
                              _p(kv_len_i32), _stream())
     _l.check(rc, "yat_pad_mask")
@@ -748,6 +785,10 @@ def pad_mask(src_cat, offsets_i32, B, T, Cdim, dst, mask_i64, key_bias_f32, kv_l
 def pack_mask(src_cat, offsets_i32, B, T, Cdim, dst_packed, mask_i64, key_bias_f32, kv_len_i32):
     """The text rows WITHOUT padding rows: dst_packed [rows_padded, C] = the source rows, then zero rows; mask / key bias /
     kv_len as ``pad_mask`` writes them (include/yat_hip.h: yat_pack_mask)."""
+    if dst_packed.dim() != 2 or dst_packed.shape[1] != Cdim:
+        raise ValueError(f"pack_mask: dst_packed must be [rows_padded, {Cdim}]")
+    _chk_text_rows("pack_mask", src_cat, offsets_i32, B, T, Cdim, dst_packed, dst_packed.numel(), mask_i64, key_bias_f32,
+                   kv_len_i32)
     rc = _lib().yat_pack_mask(B, T, Cdim, dst_packed.shape[0], _p(src_cat), _p(offsets_i32), _p(dst_packed), _p(mask_i64),
                               _p(key_bias_f32), _p(kv_len_i32), _stream())
     _l.check(rc, "yat_pack_mask")
@@ -756,6 +797,8 @@ def pack_mask(src_cat, offsets_i32, B, T, Cdim, dst_packed, mask_i64, key_bias_f
 def flow_mix(x, noise, sigma_bf16, noisy=None, target=None):
     B = x.shape[0]
     per = x.numel() // B
+    _chk_dense("flow_mix", BF16, x.numel(), x=x, noise=noise, noisy=noisy, target=target)
+    _chk_dense("flow_mix", BF16, B, sigma_bf16=sigma_bf16)
     noisy = noisy if noisy is not None else torch.empty_like(x)
     target = target if target is not None else torch.empty_like(x)
     rc = _lib().yat_flow_mix(B, per, _p(x), _p(noise), _p(sigma_bf16), _p(noisy), _p(target), _stream())
@@ -764,6 +807,10 @@ def flow_mix(x, noise, sigma_bf16, noisy=None, target=None):
 
 
 def mse_fwd_bwd(pred, target, loss_f32, dpred, workspace_f32, gscale=1.0):
+    _chk_dense("mse_fwd_bwd", BF16, pred.numel(), pred=pred, target=target, dpred=dpred)
+    _chk_dense("mse_fwd_bwd", torch.float32, loss_f32=loss_f32, workspace_f32=workspace_f32)
+    if workspace_f32.numel() < 256 or loss_f32.numel() < 1:
+        raise ValueError("mse_fwd_bwd: the workspace needs 256 floats and the loss one")
     rc = _lib().yat_mse_fwd_bwd(pred.numel(), _p(pred), _p(target), gscale, _p(loss_f32), _p(dpred), _p(workspace_f32),
                                 _stream())
     _l.check(rc, "yat_mse_fwd_bwd")
