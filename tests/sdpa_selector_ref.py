@@ -27,8 +27,10 @@ Selector inputs (``build``): per (image, head) the head's columns are dealt thre
     8, exact in bf16, and nonzero in almost every column of every row.
 
 ``reference`` is attention the plain way in fp64 (scores, softmax, P V, closed-form gradients, delta = rowsum(dO * O)); it
-knows nothing of groups.  What selector inputs cannot show: the lazy-rescale branch with a stale maximum (every score is a
-winner or >= 128 below one) and accuracy on realistic score distributions; both stay with the random-data tests.
+knows nothing of groups.  What selector inputs cannot show HERE: the lazy-rescale branch with a stale maximum (every score
+is a winner or >= 128 below one, and sdpa's scale is the model's, so no logit is an integer in log2 units) and accuracy on
+realistic score distributions; both stay with the random-data tests.  The prefill kernels that take their scale as an
+argument (Gemma, CLIP) do show that branch exactly: the ladder cases of tests/prefill_attn_ref.py.
 """
 import functools
 

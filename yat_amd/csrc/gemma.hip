@@ -116,7 +116,7 @@ constexpr int GA_MAT = 4 * GA_SUB, GA_STAGE = 2 * GA_MAT;       // K (or V) of o
 constexpr int GA_LDS = 2 * GA_STAGE;
 constexpr int GA_MAX_LEN = 1024;
 struct GemmaAttnP {
-    int rows, Hq, G, ld, ldo;
+    int rows, Hq, G, ld, ldo, max_len;
     float scale, cap;
     const bf16_t* q; const bf16_t* k; const bf16_t* v;
     const int* off;
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(NW * 64) void gemma_attn_kernel(GemmaAttnP p) {
     const int g = lane >> 4, li = lane & 15;
     const int b = blockIdx.z;
     const int prow0 = min(max(p.off[b], 0), p.rows), prow1 = min(max(p.off[b + 1], prow0), p.rows);
-    const int len = min(prow1 - prow0, GA_MAX_LEN);
+    const int len = min(prow1 - prow0, p.max_len);             // (as csrc/t5.hip, csrc/clip.hip: rows past max_len stay as they are)
     const int q0 = blockIdx.x * QT;
     if (q0 >= len) return;                                     // (the whole workgroup, before any barrier)
     const int groups = p.G / HPW;
@@ -288,7 +288,7 @@ int yat_gemma_attn_fwd(int B, int rows, int Hq, int Hkv, int dh, int max_len, fl
     if (((uintptr_t)qkv | (uintptr_t)out) & 15 || ((uintptr_t)row_offsets & 3)) return YAT_EINVAL;
     if ((int64_t)GA_MAX_LEN * ld * 2 > 0x7fffffffll || Hq > 65535) return YAT_EINVAL;   // a prompt's K / V block: one buffer resource
     GemmaAttnP p{};
-    p.rows = rows; p.Hq = Hq; p.G = Hq / Hkv; p.ld = ld; p.ldo = ldo; p.scale = scale; p.cap = softcap;
+    p.rows = rows; p.Hq = Hq; p.G = Hq / Hkv; p.ld = ld; p.ldo = ldo; p.max_len = max_len; p.scale = scale; p.cap = softcap;
     p.q = (const bf16_t*)qkv + q_off; p.k = (const bf16_t*)qkv + k_off; p.v = (const bf16_t*)qkv + v_off;
     p.off = (const int*)row_offsets; p.out = (bf16_t*)out;
     hipStream_t st = (hipStream_t)stream;

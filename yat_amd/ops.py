@@ -116,6 +116,16 @@ def _chk_bf16(*ts):
             raise TypeError(f"expected bf16, got {t.dtype}")
 
 
+def _chk_rows(op, **ts):
+    """Argument check of the wrappers that hand the library a pointer and a row stride: every tensor's last dimension is
+    contiguous.  Raises ValueError before any library call -- pointer plus ld cannot express a column stride, the kernels would
+    read (or write) such a view as if its columns were adjacent."""
+    for name, t in ts.items():
+        if t is not None and (t.dim() < 1 or (t.shape[-1] > 1 and t.stride(-1) != 1)):
+            raise ValueError(f"{op}: {name} must have a contiguous last dimension, got shape {tuple(t.shape)} "
+                             f"strides {tuple(t.stride())}")
+
+
 def _chk_dense(op, dtype, n=None, **ts):
     """Argument check of the wrappers that hand the library an element count and raw pointers: every tensor (None =
     an absent optional operand) has ``dtype``, is contiguous and, with ``n``, holds exactly ``n`` elements.  Raises
@@ -1038,6 +1048,7 @@ def vae_groupnorm(x, w, b, y, B, HW, C, G, workspace, eps=1e-6, silu=False):
 def vae_attn_fwd(q, k, v, out, B, N, dh, ld, ldo=None):
     """Single-head SDPA, scale dh^-0.5, no mask (yat_vae_attn_fwd); q / k / v are column views of a [B*N, ld] matrix."""
     _chk_bf16(q, k, v, out)
+    _chk_rows("vae_attn_fwd", q=q, k=k, v=v, out=out)
     rc = _lib().yat_vae_attn_fwd(B, N, dh, _p(q), _p(k), _p(v), int(ld), _p(out), int(ldo if ldo is not None else dh),
                                  _stream())
     _l.check(rc, "yat_vae_attn_fwd")
@@ -1092,6 +1103,7 @@ def gemma_rmsnorm(x2d, w, y, eps=1e-6, residual=None):
 def rope_qk(qkv2d, heads, dh, pos_i32, cos, sin):
     """apply_rotary_pos_emb in place on the first ``heads`` head blocks (q then k) of ``qkv2d`` (yat_rope_qk)."""
     _chk_bf16(qkv2d, cos, sin)
+    _chk_rows("rope_qk", qkv2d=qkv2d)
     if pos_i32.dtype != torch.int32 or pos_i32.numel() != qkv2d.shape[0] or tuple(cos.shape) != tuple(sin.shape) \
             or cos.shape[1] != dh:
         raise ValueError("rope_qk: int32 positions, one per row, and [max_len, dh] tables")
@@ -1104,6 +1116,7 @@ def rope_qk(qkv2d, heads, dh, pos_i32, cos, sin):
 def geglu(gate_up2d, N, out):
     """out = bf16(bf16(gelu_tanh(gate)) * up) for gate_up2d = [gate | up] (N columns each) (yat_geglu)."""
     _chk_bf16(gate_up2d, out)
+    _chk_rows("geglu", gate_up2d=gate_up2d, out=out)
     rc = _lib().yat_geglu(gate_up2d.shape[0], N, _p(gate_up2d), _p(gate_up2d[:, N:]), gate_up2d.stride(0), _p(out),
                           out.stride(0), _stream())
     _l.check(rc, "yat_geglu")
@@ -1114,6 +1127,7 @@ def gemma_attn_fwd(qkv2d, row_offsets_i32, B, Hq, Hkv, dh, max_len, scale, softc
     """Causal grouped-query soft-capped attention over packed prompts (yat_gemma_attn_fwd); qkv2d = [q | k | v] blocks,
     ``row_offsets_i32``: int32 [B + 1] on the device, ``max_len`` >= the longest prompt, ``softcap`` 0 = none."""
     _chk_bf16(qkv2d, out)
+    _chk_rows("gemma_attn_fwd", qkv2d=qkv2d, out=out)
     if row_offsets_i32.dtype != torch.int32 or row_offsets_i32.numel() != B + 1:
         raise ValueError("gemma_attn_fwd: row_offsets must be int32 [B + 1]")
     rc = _lib().yat_gemma_attn_fwd(B, qkv2d.shape[0], Hq, Hkv, dh, int(max_len), float(scale), float(softcap or 0.0),
@@ -1141,6 +1155,7 @@ def t5_attn_fwd(qkv2d, row_offsets_i32, B, H, dh, max_len, bias_rel, out):
     """Bidirectional unscaled attention with T5's relative-position bias over packed prompts (yat_t5_attn_fwd); qkv2d =
     [q | k | v] blocks, ``row_offsets_i32``: int32 [B + 1] on the device, ``bias_rel``: bf16 [H, 2 * max_len - 1]."""
     _chk_bf16(qkv2d, bias_rel, out)
+    _chk_rows("t5_attn_fwd", qkv2d=qkv2d, out=out)
     if row_offsets_i32.dtype != torch.int32 or row_offsets_i32.numel() != B + 1:
         raise ValueError("t5_attn_fwd: row_offsets must be int32 [B + 1]")
     if bias_rel.dim() != 2 or not bias_rel.is_contiguous() or bias_rel.shape[0] != H or bias_rel.shape[1] != 2 * int(max_len) - 1:
@@ -1206,6 +1221,7 @@ def clip_attn_fwd(qkv2d, row_offsets_i32, B, H, dh, max_len, scale, out):
     """Causal scaled attention over packed prompts (yat_clip_attn_fwd); qkv2d = [q | k | v] blocks, ``row_offsets_i32``: int32
     [B + 1] on the device, ``max_len`` >= the longest prompt."""
     _chk_bf16(qkv2d, out)
+    _chk_rows("clip_attn_fwd", qkv2d=qkv2d, out=out)
     if row_offsets_i32.dtype != torch.int32 or row_offsets_i32.numel() != B + 1:
         raise ValueError("clip_attn_fwd: row_offsets must be int32 [B + 1]")
     rc = _lib().yat_clip_attn_fwd(B, qkv2d.shape[0], H, dh, int(max_len), _p(qkv2d), qkv2d.stride(0), 0, H * dh, 2 * H * dh,
