@@ -470,11 +470,13 @@ int yat_gradnorm_pieces_partial(const void* grad, int npiece, const int64_t* pie
                                 int max_piece_chunks, const unsigned char* owned, float* partial, yat_stream_t stream);
 int yat_gradnorm_pieces_finish(int ntensor, const int* tensor_first_piece, const int* chunk_base, const float* partial,
                                float max_norm, float* norm_out, float* clip_coef, yat_stream_t stream);
-/* background: 0 = full-width launch (the update alone on the GPU); N > 0 = at most N workgroups of a 48-VGPR variant
- * that can share a CU with two resident GEMM waves -- for an update that runs under the next forward's GEMMs. */
+/* The bf16 step: all five buffers bf16 (ema_shadow or NULL), 14 B / parameter (18 with the shadow).  One full-width launch:
+ * 8 parameters per lane and iteration, non-temporal accesses to the state, a grid capped at 8192 workgroups -- the launch shape
+ * of all three steps.  n % 8 == 0; every buffer 16-byte aligned.  YAT_EINVAL before any launch for n <= 0, n % 8, step < 1 or
+ * a NULL param / grad / exp_avg / exp_avg_sq. */
 int yat_adamw_step(int64_t n, void* param, void* grad, void* exp_avg, void* exp_avg_sq, const float* clip_coef,
                    double lr, double beta1, double beta2, double eps, double weight_decay, int step, int zero_grad,
-                   void* ema_shadow, double ema_decay, int background, yat_stream_t stream);
+                   void* ema_shadow, double ema_decay, yat_stream_t stream);
 /* The mixed-precision form of the same step: fp32 master weights, fp32 exp_avg / exp_avg_sq and an fp32 EMA shadow (or
  * NULL); gradients stay bf16 and param_bf16 -- the buffer every forward and backward kernel reads -- is written in the same
  * pass as bf16(master) (round to nearest even, NaN kept).  torch's single-tensor AdamW op sequence on fp32 tensors, no

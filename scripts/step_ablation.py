@@ -24,7 +24,7 @@ FAMILIES = {
     "sdpa": {"sdpa_fwd": "out", "sdpa_bwd": None},
     "dwfwd": {"dwconv_glu_fwd": "y"},
     "dwbwd": {"dwconv_glu_bwd": None},
-    "adamw": {"gradnorm_clip": None, "adamw_step": None},
+    "adamw": {"gradnorm_pieces_partial": None, "gradnorm_pieces_finish": None, "adamw_step": None},
 }
 
 

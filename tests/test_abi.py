@@ -67,8 +67,32 @@ def test_bad_arguments_are_rejected_without_a_gpu(built_lib):
     # argument validation happens before any launch, so it is testable on the CPU box
     assert lib.yat_gemm_bf16(0, 0, 0, 8, 8, None, 8, None, 8, None, 8, None, None) == -1
     assert lib.yat_gemm_bf16(0, 0, 8, 8, 12, 1, 16, 1, 16, 1, 8, None, None) == -1  # K % 8 != 0
-    assert lib.yat_adamw_step(7, 1, 1, 1, 1, None, 1e-4, 0.9, 0.999, 1e-8, 0.0, 1, 1, None, 0.0, 0, None) == -1
+    assert lib.yat_adamw_step(7, 1, 1, 1, 1, None, 1e-4, 0.9, 0.999, 1e-8, 0.0, 1, 1, None, 0.0, None) == -1
     assert lib.yat_ln_modulate_fwd(4, 7, 4, 1e-6, 1, 1, 1, 8, 1, 1, 1, None) == -1     # D % 8 != 0
+
+
+def test_adamw_steps_share_one_argument_check(built_lib):
+    """The three AdamW entry points (include/yat_hip.h) refuse the same argument errors through one host helper, before any
+    launch -- no GPU needed: an empty or ragged element count, a bias-correction step below 1 and every required buffer NULL
+    in turn; yat_adamw_sr_step adds its own (elem_offset, rng_step)."""
+    lib = ylib.load()
+    hyp = (None, 1e-4, 0.9, 0.999, 1e-8, 0.01)          # clip_coef (optional), lr, beta1, beta2, eps, weight_decay
+
+    def call(name, n=64, step=1, null=None, seed=0, rng_step=0, elem_offset=0):
+        nbuf = 5 if name == "yat_adamw_master_step" else 4              # master: param_bf16, master, grad_bf16, exp_avg, exp_avg_sq
+        bufs = [None if i == null else 1 for i in range(nbuf)]         # (dummy non-NULL pointers: nothing is launched)
+        extra = (seed, rng_step, elem_offset) if name == "yat_adamw_sr_step" else ()
+        return getattr(lib, name)(n, *bufs, *hyp, step, 0, None, 0.0, *extra, None)
+
+    for name, nbuf in (("yat_adamw_step", 4), ("yat_adamw_master_step", 5), ("yat_adamw_sr_step", 4)):
+        assert call(name, n=0) == -1, name
+        assert call(name, n=7) == -1, name
+        assert call(name, step=0) == -1, name
+        for i in range(nbuf):
+            assert call(name, null=i) == -1, (name, i)
+    assert call("yat_adamw_sr_step", elem_offset=-8) == -1
+    assert call("yat_adamw_sr_step", elem_offset=4) == -1
+    assert call("yat_adamw_sr_step", rng_step=-1) == -1
 
 
 def test_lokr_rows_bwd_rejects_chunk_counts_whose_index_would_wrap(built_lib):

@@ -28,7 +28,7 @@ from test_kernels_gpu import BF, DEV, _collect_failures, ops  # noqa: F401  (fix
 pytestmark = pytest.mark.gpu
 
 CHUNK = 1 << 18                     # csrc/optim.hip NORM_CHUNK
-GRID_PASS = 8192 * 256 * 8          # elements one pass of the AdamW grid covers (YAT_ADAMW_BLOCKS x 256 lanes x 8)
+GRID_PASS = 8192 * 256 * 8          # elements one pass of the AdamW grid covers (csrc/optim.hip STEP_MAX_BLOCKS x 256 lanes x 8)
 
 # ------------------------------------------------------------------------------------------------ helpers
 def _up(x, a):

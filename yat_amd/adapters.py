@@ -46,6 +46,12 @@ class SlabColumns:
             i, col = i + 1, 0
         if i == len(slabs) or slabs[i].shape[0] < M:
             buf = torch.zeros(M, K, dtype=BF16, device=self.device)
+            # the fill runs on the stream that happens to create the slab; later slots are written and read on other streams
+            # (forward chains, the weight-gradient stream) that are not ordered behind it -- a fill that lands late wipes a T1
+            # between the forward that wrote it and the backward that reads it.  Creation is rare (first step, or a larger
+            # batch than any before): wait for the fill here, once
+            if buf.is_cuda:
+                torch.cuda.current_stream().synchronize()
             if i == len(slabs):
                 slabs.append(buf)
             else:

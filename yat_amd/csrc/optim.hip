@@ -1,16 +1,60 @@
-// Fused optimizer step for gfx950 over ONE flat bf16 parameter buffer:
+// The optimizer of the step loop over ONE flat parameter buffer, for gfx950:
 //   global gradient-norm clip (torch.nn.utils.clip_grad_norm_, common/trainer.py:347)
 //   + AdamW (torch.optim.AdamW, common/trainer.py:246-248,348) + zero_grad (:356) + optional EMA (:350-351).
-// HBM-bound: 14 B/param algorithmic traffic (read p,g,m,v; write p,m,v) + 2 B for the grad clear.
-// The arithmetic follows torch's single-tensor op sequence on bf16 tensors: every torch op
-// computes in fp32 and rounds its result to bf16, so the kernel rounds at the same points.
+// The norm: per-chunk sums of squares, then one workgroup that applies torch's clip arithmetic -- over SEGMENTS (whole tensors,
+//   yat_gradnorm_clip) and over PIECES (tensors cut at the eighths of their data-parallel bucket, yat_gradnorm_pieces_*: what
+//   FlatAdamW calls, and what a sharded step can split over ranks); both forms share the chunk sum and the clip tail.
+// The bf16 step (adamw_kernel, yat_adamw_step): all state bf16, 14 B / parameter of algorithmic traffic (read p, g, m, v;
+//   write p, m, v) + 2 B for the gradient clear.  The arithmetic follows torch's single-tensor op sequence on bf16 tensors:
+//   every torch op computes in fp32 and rounds its result to bf16, so the kernel rounds at the same points.
+// Two opt-in steps that answer the stall of sub-ulp updates: fp32 master weights (adamw_master_kernel, 28 B / parameter) and
+//   stochastic rounding of an all-bf16 state (adamw_sr_kernel, 14 B / parameter, Philox bits made in registers).
+// The three steps are HBM-bound streams of 16-byte accesses with one launch shape: 8 parameters per lane and iteration, a
+//   grid-stride loop over a grid capped at STEP_MAX_BLOCKS.
 #include "common.hpp"
 #include "../../include/yat_hip.h"
 #include <math.h>
+#include <initializer_list>
 
 namespace {
 
 constexpr int64_t NORM_CHUNK = 1 << 18;  // elements per gradnorm workgroup
+
+// sum over the 256 lanes of a workgroup, the four wave sums added in wave order
+__device__ __forceinline__ float block_sum(float s) {
+    __shared__ float red[4];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+// one workgroup's sum of squares of g[c0, c1): 16-byte vector body (chunk starts are 16-B aligned) + scalar tail
+__device__ __forceinline__ float chunk_sumsq(const bf16_t* g, int64_t c0, int64_t c1) {
+    float s = 0.f;
+    const int64_t nvec = (c1 - c0) >> 3;
+    for (int64_t i = threadIdx.x; i < nvec; i += 256) {
+        float v[8];
+        unpack8(*reinterpret_cast<const u32x4*>(g + c0 + i * 8), v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s += v[e] * v[e];
+    }
+    for (int64_t i = c0 + (nvec << 3) + threadIdx.x; i < c1; i += 256) { const float v = bf2f(g[i]); s += v * v; }
+    return block_sum(s);
+}
+
+// the end of both finish kernels: acc = this lane's sum of squared per-tensor norms -> total norm and clip coefficient,
+// torch's clip_grad_norm_ arithmetic on bf16 gradients (every intermediate is a bf16 tensor)
+__device__ __forceinline__ void clip_tail(float acc, float max_norm, float* norm_out, float* clip_coef) {
+    const float sum = block_sum(acc);
+    if (threadIdx.x == 0) {
+        const float total = rbf(sqrtf(sum));
+        float coef = rbf(max_norm / rbf(total + 1e-6f));
+        coef = coef > 1.0f ? 1.0f : coef;   // torch.clamp(max=1.0) keeps a NaN (fminf would give 1)
+        norm_out[0] = total;
+        clip_coef[0] = coef;
+    }
+}
 
 // grid = (maxchunks, nseg): sum of squares of one chunk of one parameter tensor
 __global__ __launch_bounds__(256) void gradnorm_partial_kernel(const bf16_t* g, const int64_t* seg_start, int maxchunks,
@@ -20,21 +64,8 @@ __global__ __launch_bounds__(256) void gradnorm_partial_kernel(const bf16_t* g, 
     const int64_t c0 = s0 + (int64_t)ck * NORM_CHUNK;
     if (c0 >= s1) return;
     const int64_t c1 = (c0 + NORM_CHUNK < s1) ? c0 + NORM_CHUNK : s1;
-    float s = 0.f;
-    // segment starts are 16-B aligned; vector body + scalar tail
-    const int64_t nvec = (c1 - c0) >> 3;
-    for (int64_t i = threadIdx.x; i < nvec; i += 256) {
-        float v[8];
-        unpack8(*reinterpret_cast<const u32x4*>(g + c0 + i * 8), v);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += v[e] * v[e];
-    }
-    for (int64_t i = c0 + (nvec << 3) + threadIdx.x; i < c1; i += 256) { const float v = bf2f(g[i]); s += v * v; }
-    __shared__ float red[4];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[(int64_t)seg * maxchunks + ck] = red[0] + red[1] + red[2] + red[3];
+    const float s = chunk_sumsq(g, c0, c1);
+    if (threadIdx.x == 0) partial[(int64_t)seg * maxchunks + ck] = s;
 }
 
 __global__ __launch_bounds__(256) void gradnorm_final_kernel(int nseg, const int64_t* seg_start, int maxchunks,
@@ -49,17 +80,7 @@ __global__ __launch_bounds__(256) void gradnorm_final_kernel(int nseg, const int
         const float nb = rbf(sqrtf(s));   // per-tensor norm comes back as a bf16 tensor
         acc += nb * nb;
     }
-    __shared__ float red[4];
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float total = rbf(sqrtf(red[0] + red[1] + red[2] + red[3]));
-        float coef = rbf(max_norm / rbf(total + 1e-6f));
-        coef = coef > 1.0f ? 1.0f : coef;   // torch.clamp(max=1.0) keeps a NaN (fminf would give 1)
-        norm_out[0] = total;
-        clip_coef[0] = coef;
-    }
+    clip_tail(acc, max_norm, norm_out, clip_coef);
 }
 
 // ---- the same norm over PIECES (round 6): a piece is a tensor, or the part of a tensor inside one eighth of its
@@ -81,20 +102,8 @@ __global__ __launch_bounds__(256) void gradnorm_pieces_partial_kernel(const bf16
     const int64_t s1 = piece_start[pc + 1];
     const int64_t c0 = piece_start[pc] + (int64_t)ck * NORM_CHUNK;
     const int64_t c1 = (c0 + NORM_CHUNK < s1) ? c0 + NORM_CHUNK : s1;
-    float s = 0.f;
-    const int64_t nvec = (c1 - c0) >> 3;
-    for (int64_t i = threadIdx.x; i < nvec; i += 256) {
-        float v[8];
-        unpack8(*reinterpret_cast<const u32x4*>(g + c0 + i * 8), v);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += v[e] * v[e];
-    }
-    for (int64_t i = c0 + (nvec << 3) + threadIdx.x; i < c1; i += 256) { const float v = bf2f(g[i]); s += v * v; }
-    __shared__ float red[4];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) *dst = red[0] + red[1] + red[2] + red[3];
+    const float s = chunk_sumsq(g, c0, c1);
+    if (threadIdx.x == 0) *dst = s;
 }
 
 __global__ __launch_bounds__(256) void gradnorm_pieces_final_kernel(int ntensor, const int* tensor_first_piece,
@@ -111,17 +120,7 @@ __global__ __launch_bounds__(256) void gradnorm_pieces_final_kernel(int ntensor,
         const float nb = rbf(sqrtf(s));   // per-tensor norm comes back as a bf16 tensor
         acc += nb * nb;
     }
-    __shared__ float red[4];
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float total = rbf(sqrtf(red[0] + red[1] + red[2] + red[3]));
-        float coef = rbf(max_norm / rbf(total + 1e-6f));
-        coef = coef > 1.0f ? 1.0f : coef;   // torch.clamp(max=1.0) keeps a NaN (fminf would give 1)
-        norm_out[0] = total;
-        clip_coef[0] = coef;
-    }
+    clip_tail(acc, max_norm, norm_out, clip_coef);
 }
 
 struct AdamP {
@@ -144,38 +143,34 @@ __device__ __forceinline__ void adamw_elem(float& pr, float g, float& mr_, float
     vr_ = vr;
 }
 
-template <int U, bool NT>
+constexpr int STEP_MAX_BLOCKS = 8192;        // x 256 lanes x 8 parameters = 2^24 parameters per grid pass (yat_amd/optim.py MASTER_GRID_PASS)
+
+// U = 1 vector of 8 parameters per thread and iteration, every load of the iteration issued before the first use (4 or 5
+// independent 16-byte loads in flight per lane), grid capped at STEP_MAX_BLOCKS.  The state streams through once per step, so
+// its accesses are non-temporal: measured alone the plain and the non-temporal form (and U = 2) are equal; in the step the
+// non-temporal form is 0.3 ms shorter -- 22 GB of state do not sweep the Infinity Cache of what the forward that runs beside
+// this kernel re-reads.  A 48-VGPR form of it (a few persistent workgroups that share a CU with two resident GEMM waves,
+// for an update that runs under the next forward) was measured and rejected in round 3.
+// The load block and the arithmetic block stay loops over the (one) vector: written straight-line the compiler resolves the
+// optional shadow load before it unrolls and emits a loop that, with a shadow, waits for all five loads before the first
+// parameter's arithmetic (4 instructions more) instead of this one, which starts on g, v, m, p as they arrive.
 __global__ __launch_bounds__(256) void adamw_kernel(int64_t nvec, bf16_t* p, bf16_t* g, bf16_t* m, bf16_t* v,
                                                     const float* clip_coef, bf16_t* ema, AdamP a) {
-    // U vectors of 8 parameters per thread and iteration, every load of the iteration issued before the first use (4 U
-    // independent 16-byte loads in flight per lane); NT: the state streams through once per step -- non-temporal accesses
-    // keep 22 GB of it from evicting what the forward that runs beside this kernel re-reads.
+    constexpr int U = 1;
     const float coef = clip_coef ? clip_coef[0] : 1.0f;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < nvec; i0 += stride * U) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
         u32x4 rp[U], rg[U], rm[U], rv[U], rs[U];
 #pragma unroll
         for (int q = 0; q < U; ++q) {
-            const int64_t i = i0 + q * stride;
-            if (i < nvec) {
-                if (NT) {
-                    rp[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + i * 8));
-                    rg[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(g + i * 8));
-                    rm[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(m + i * 8));
-                    rv[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(v + i * 8));
-                } else {
-                    rp[q] = *reinterpret_cast<const u32x4*>(p + i * 8);
-                    rg[q] = *reinterpret_cast<const u32x4*>(g + i * 8);
-                    rm[q] = *reinterpret_cast<const u32x4*>(m + i * 8);
-                    rv[q] = *reinterpret_cast<const u32x4*>(v + i * 8);
-                }
-                if (ema) rs[q] = *reinterpret_cast<const u32x4*>(ema + i * 8);
-            }
+            rp[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + i * 8));
+            rg[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(g + i * 8));
+            rm[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(m + i * 8));
+            rv[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(v + i * 8));
+            if (ema) rs[q] = *reinterpret_cast<const u32x4*>(ema + i * 8);
         }
 #pragma unroll
         for (int q = 0; q < U; ++q) {
-            const int64_t i = i0 + q * stride;
-            if (i >= nvec) continue;
             float pp[8], gg[8], mm[8], vv[8], ss[8];
             unpack8(rp[q], pp);
             unpack8(rg[q], gg);
@@ -190,47 +185,12 @@ __global__ __launch_bounds__(256) void adamw_kernel(int64_t nvec, bf16_t* p, bf1
                     ss[e] = rbf(ss[e] - rbf(a.ema_omd * d));
                 }
             }
-            if (NT) {
-                __builtin_nontemporal_store(pack8(pp), reinterpret_cast<u32x4*>(p + i * 8));
-                __builtin_nontemporal_store(pack8(mm), reinterpret_cast<u32x4*>(m + i * 8));
-                __builtin_nontemporal_store(pack8(vv), reinterpret_cast<u32x4*>(v + i * 8));
-            } else {
-                *reinterpret_cast<u32x4*>(p + i * 8) = pack8(pp);
-                *reinterpret_cast<u32x4*>(m + i * 8) = pack8(mm);
-                *reinterpret_cast<u32x4*>(v + i * 8) = pack8(vv);
-            }
+            __builtin_nontemporal_store(pack8(pp), reinterpret_cast<u32x4*>(p + i * 8));
+            __builtin_nontemporal_store(pack8(mm), reinterpret_cast<u32x4*>(m + i * 8));
+            __builtin_nontemporal_store(pack8(vv), reinterpret_cast<u32x4*>(v + i * 8));
             if (ema) *reinterpret_cast<u32x4*>(ema + i * 8) = pack8(ss);
             if (a.zero_grad) *reinterpret_cast<u32x4*>(g + i * 8) = u32x4{0u, 0u, 0u, 0u};
         }
-    }
-}
-
-// Background variant for the update that runs UNDER the next forward: one 256-thread workgroup per CU, 4 elements per
-// thread and iteration, capped at 48 VGPRs -- what two resident waves of a 256-row GEMM workgroup (<= 232 VGPRs each)
-// leave free on a SIMD, so it can share a CU with the GEMM instead of queueing for a whole one.  Same arithmetic.
-__global__ __launch_bounds__(256, 10) void adamw_bg_kernel(int64_t nvec4, bf16_t* p, bf16_t* g, bf16_t* m, bf16_t* v,
-                                                           const float* clip_coef, bf16_t* ema, AdamP a) {
-    const float coef = clip_coef ? clip_coef[0] : 1.0f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec4; i += (int64_t)gridDim.x * blockDim.x) {
-        float pp[4], gg[4], mm[4], vv[4], ss[4];
-        unpack4(*reinterpret_cast<const u32x2*>(p + i * 4), pp);
-        unpack4(*reinterpret_cast<const u32x2*>(g + i * 4), gg);
-        unpack4(*reinterpret_cast<const u32x2*>(m + i * 4), mm);
-        unpack4(*reinterpret_cast<const u32x2*>(v + i * 4), vv);
-        if (ema) unpack4(*reinterpret_cast<const u32x2*>(ema + i * 4), ss);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            adamw_elem(pp[e], gg[e], mm[e], vv[e], coef, clip_coef != nullptr, a);
-            if (ema) {
-                const float d = rbf(ss[e] - pp[e]);
-                ss[e] = rbf(ss[e] - rbf(a.ema_omd * d));
-            }
-        }
-        *reinterpret_cast<u32x2*>(p + i * 4) = pack4(pp[0], pp[1], pp[2], pp[3]);
-        *reinterpret_cast<u32x2*>(m + i * 4) = pack4(mm[0], mm[1], mm[2], mm[3]);
-        *reinterpret_cast<u32x2*>(v + i * 4) = pack4(vv[0], vv[1], vv[2], vv[3]);
-        if (ema) *reinterpret_cast<u32x2*>(ema + i * 4) = pack4(ss[0], ss[1], ss[2], ss[3]);
-        if (a.zero_grad) *reinterpret_cast<u32x2*>(g + i * 4) = u32x2{0u, 0u};
     }
 }
 
@@ -259,8 +219,6 @@ __device__ __forceinline__ void store8f(float* dst, const float* f) {
     __builtin_nontemporal_store(f32x4{f[0], f[1], f[2], f[3]}, reinterpret_cast<f32x4*>(dst));
     __builtin_nontemporal_store(f32x4{f[4], f[5], f[6], f[7]}, reinterpret_cast<f32x4*>(dst) + 1);
 }
-
-constexpr int MASTER_MAX_BLOCKS = 8192;      // x 256 lanes x 8 parameters = 2^24 parameters per grid pass (yat_amd/optim.py MASTER_GRID_PASS)
 
 // 8 parameters per thread and iteration, 16 bytes per access: 2 loads each of master, m, v (and the shadow) + 1 of the
 // gradients, all issued before the first use (7 or 9 independent loads in flight per lane); 28 B / parameter, 36 with EMA.
@@ -324,8 +282,8 @@ __device__ __forceinline__ uint32_t sr_bf16(float x, uint32_t r) {          // r
     return (u & 0x7f800000u) != 0x7f800000u ? (u + r) >> 16 : (uint32_t)f2bf(x);
 }
 
-// adamw_kernel<1, true>'s shape: 8 parameters per lane and iteration, the four (five) 16-byte loads issued before the first
-// use, non-temporal, grid capped at MASTER_MAX_BLOCKS with a grid-stride loop; four Philox calls per 8-parameter vector.
+// adamw_kernel's shape: 8 parameters per lane and iteration, the four (five) 16-byte loads issued before the first use,
+// non-temporal, grid capped at STEP_MAX_BLOCKS with a grid-stride loop; four Philox calls per 8-parameter vector.
 __global__ __launch_bounds__(256) void adamw_sr_kernel(int64_t nvec, bf16_t* p, bf16_t* g, bf16_t* m, bf16_t* v,
                                                        const float* clip_coef, bf16_t* ema, AdamP a, uint32_t seed_lo,
                                                        uint32_t seed_hi, uint32_t step_lo, uint32_t step_hi, int64_t pair0) {
@@ -440,34 +398,32 @@ static AdamP adam_scalars(double lr, double beta1, double beta2, double eps, dou
     return a;
 }
 
+// what the three step entry points share: the argument check (before any launch), the scalars and the capped grid
+struct StepLaunch {
+    AdamP a;
+    int64_t nvec;
+    unsigned blocks;
+};
+static bool step_launch(StepLaunch& L, int64_t n, std::initializer_list<const void*> required, double lr, double beta1,
+                        double beta2, double eps, double weight_decay, int step, int zero_grad, double ema_decay) {
+    if (n <= 0 || (n & 7) || step < 1) return false;
+    for (const void* buf : required)
+        if (!buf) return false;
+    L.a = adam_scalars(lr, beta1, beta2, eps, weight_decay, step, zero_grad, ema_decay);
+    L.nvec = n >> 3;
+    const int64_t nb = (L.nvec + 255) / 256;
+    L.blocks = (unsigned)(nb > STEP_MAX_BLOCKS ? STEP_MAX_BLOCKS : nb);
+    return true;
+}
+
 int yat_adamw_step(int64_t n, void* param, void* grad, void* exp_avg, void* exp_avg_sq, const float* clip_coef, double lr,
                    double beta1, double beta2, double eps, double weight_decay, int step, int zero_grad, void* ema_shadow,
-                   double ema_decay, int background, yat_stream_t stream) {
-    if (n <= 0 || (n & 7) || step < 1 || !param || !grad || !exp_avg || !exp_avg_sq) return YAT_EINVAL;
-    const AdamP a = adam_scalars(lr, beta1, beta2, eps, weight_decay, step, zero_grad, ema_decay);
-    if (background) {
-        const int64_t nvec4 = n >> 2;
-        int64_t nbg = (nvec4 + 255) / 256;
-        if (nbg > background) nbg = background;                 // `background` = workgroups (e.g. 256: one per CU)
-        hipLaunchKernelGGL(adamw_bg_kernel, dim3((unsigned)nbg), dim3(256), 0, (hipStream_t)stream, nvec4, (bf16_t*)param,
-                           (bf16_t*)grad, (bf16_t*)exp_avg, (bf16_t*)exp_avg_sq, clip_coef, (bf16_t*)ema_shadow, a);
-        YAT_CHECK_LAUNCH();
-        return YAT_OK;
-    }
-    const int64_t nvec = n >> 3;
-    static const int variant = YAT_TUNE_INT("YAT_ADAMW_VARIANT", 3);      // 0: one vector per iteration; 1: two; 2: two, non-temporal; 3: one, non-temporal (alone all four are equal; in the step the non-temporal form is 0.3 ms shorter: the 22 GB of state do not sweep the Infinity Cache under the next forward)
-    static const int max_blocks = YAT_TUNE_INT("YAT_ADAMW_BLOCKS", 8192);
-    const int U = (variant == 1 || variant == 2) ? 2 : 1;
-    int64_t nb = (nvec + 256 * U - 1) / (256 * U);
-    if (nb > max_blocks) nb = max_blocks;
-#define YAT_ADAMW_LAUNCH(UU, NTT)                                                                                            \
-    hipLaunchKernelGGL((adamw_kernel<UU, NTT>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, nvec, (bf16_t*)param, \
-                       (bf16_t*)grad, (bf16_t*)exp_avg, (bf16_t*)exp_avg_sq, clip_coef, (bf16_t*)ema_shadow, a)
-    if (variant == 1) YAT_ADAMW_LAUNCH(2, false);
-    else if (variant == 2) YAT_ADAMW_LAUNCH(2, true);
-    else if (variant == 3) YAT_ADAMW_LAUNCH(1, true);
-    else YAT_ADAMW_LAUNCH(1, false);
-#undef YAT_ADAMW_LAUNCH
+                   double ema_decay, yat_stream_t stream) {
+    StepLaunch L;
+    if (!step_launch(L, n, {param, grad, exp_avg, exp_avg_sq}, lr, beta1, beta2, eps, weight_decay, step, zero_grad, ema_decay))
+        return YAT_EINVAL;
+    hipLaunchKernelGGL(adamw_kernel, dim3(L.blocks), dim3(256), 0, (hipStream_t)stream, L.nvec, (bf16_t*)param, (bf16_t*)grad,
+                       (bf16_t*)exp_avg, (bf16_t*)exp_avg_sq, clip_coef, (bf16_t*)ema_shadow, L.a);
     YAT_CHECK_LAUNCH();
     return YAT_OK;
 }
@@ -475,13 +431,12 @@ int yat_adamw_step(int64_t n, void* param, void* grad, void* exp_avg, void* exp_
 int yat_adamw_master_step(int64_t n, void* param_bf16, float* master, void* grad_bf16, float* exp_avg, float* exp_avg_sq,
                           const float* clip_coef, double lr, double beta1, double beta2, double eps, double weight_decay,
                           int step, int zero_grad, float* ema_shadow, double ema_decay, yat_stream_t stream) {
-    if (n <= 0 || (n & 7) || step < 1 || !param_bf16 || !master || !grad_bf16 || !exp_avg || !exp_avg_sq) return YAT_EINVAL;
-    const AdamP a = adam_scalars(lr, beta1, beta2, eps, weight_decay, step, zero_grad, ema_decay);
-    const int64_t nvec = n >> 3;
-    int64_t nb = (nvec + 255) / 256;
-    if (nb > MASTER_MAX_BLOCKS) nb = MASTER_MAX_BLOCKS;
-    hipLaunchKernelGGL(adamw_master_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, nvec, (bf16_t*)param_bf16,
-                       master, (bf16_t*)grad_bf16, exp_avg, exp_avg_sq, clip_coef, ema_shadow, a);
+    StepLaunch L;
+    if (!step_launch(L, n, {param_bf16, master, grad_bf16, exp_avg, exp_avg_sq}, lr, beta1, beta2, eps, weight_decay, step,
+                     zero_grad, ema_decay))
+        return YAT_EINVAL;
+    hipLaunchKernelGGL(adamw_master_kernel, dim3(L.blocks), dim3(256), 0, (hipStream_t)stream, L.nvec, (bf16_t*)param_bf16,
+                       master, (bf16_t*)grad_bf16, exp_avg, exp_avg_sq, clip_coef, ema_shadow, L.a);
     YAT_CHECK_LAUNCH();
     return YAT_OK;
 }
@@ -489,15 +444,12 @@ int yat_adamw_master_step(int64_t n, void* param_bf16, float* master, void* grad
 int yat_adamw_sr_step(int64_t n, void* param, void* grad, void* exp_avg, void* exp_avg_sq, const float* clip_coef, double lr,
                       double beta1, double beta2, double eps, double weight_decay, int step, int zero_grad, void* ema_shadow,
                       double ema_decay, uint64_t seed, int64_t rng_step, int64_t elem_offset, yat_stream_t stream) {
-    if (n <= 0 || (n & 7) || elem_offset < 0 || (elem_offset & 7) || rng_step < 0 || step < 1 || !param || !grad || !exp_avg ||
-        !exp_avg_sq)
+    StepLaunch L;
+    if (elem_offset < 0 || (elem_offset & 7) || rng_step < 0 ||
+        !step_launch(L, n, {param, grad, exp_avg, exp_avg_sq}, lr, beta1, beta2, eps, weight_decay, step, zero_grad, ema_decay))
         return YAT_EINVAL;
-    const AdamP a = adam_scalars(lr, beta1, beta2, eps, weight_decay, step, zero_grad, ema_decay);
-    const int64_t nvec = n >> 3;
-    int64_t nb = (nvec + 255) / 256;
-    if (nb > MASTER_MAX_BLOCKS) nb = MASTER_MAX_BLOCKS;
-    hipLaunchKernelGGL(adamw_sr_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, nvec, (bf16_t*)param,
-                       (bf16_t*)grad, (bf16_t*)exp_avg, (bf16_t*)exp_avg_sq, clip_coef, (bf16_t*)ema_shadow, a, (uint32_t)seed,
+    hipLaunchKernelGGL(adamw_sr_kernel, dim3(L.blocks), dim3(256), 0, (hipStream_t)stream, L.nvec, (bf16_t*)param,
+                       (bf16_t*)grad, (bf16_t*)exp_avg, (bf16_t*)exp_avg_sq, clip_coef, (bf16_t*)ema_shadow, L.a, (uint32_t)seed,
                        (uint32_t)(seed >> 32), (uint32_t)rng_step, (uint32_t)((uint64_t)rng_step >> 32), elem_offset >> 1);
     YAT_CHECK_LAUNCH();
     return YAT_OK;

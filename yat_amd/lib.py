@@ -111,7 +111,7 @@ SIGNATURES = {
     "yat_gradnorm_clip": (I, [I64, P, I, P, F, P, P, P, P]),
     "yat_gradnorm_pieces_partial": (I, [P, I, P, P, I, P, P, P]),
     "yat_gradnorm_pieces_finish": (I, [I, P, P, P, F, P, P, P]),
-    "yat_adamw_step": (I, [I64, P, P, P, P, P, D, D, D, D, D, I, I, P, D, I, P]),
+    "yat_adamw_step": (I, [I64, P, P, P, P, P, D, D, D, D, D, I, I, P, D, P]),
     "yat_adamw_master_step": (I, [I64, P, P, P, P, P, P, D, D, D, D, D, I, I, P, D, P]),
     "yat_adamw_sr_step": (I, [I64, P, P, P, P, P, D, D, D, D, D, I, I, P, D, U64, I64, I64, P]),
     "yat_dcae_conv3x3": (I, [I, I, I, I, I, I, I, P, P, P, I, P, I, P, I, P, P]),

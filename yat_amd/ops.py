@@ -898,11 +898,19 @@ def gradnorm_pieces_finish(tensor_first_piece_i32, chunk_base_i32, partial_f32, 
     _l.check(rc, "yat_gradnorm_pieces_finish")
 
 
+def _chk_step(op, param, bf16, f32=None):
+    """Argument check of the three AdamW steps: ``param`` is bf16 and contiguous, and every buffer of ``bf16`` / ``f32`` that
+    is not None has that dtype, is contiguous and has the parameters' size.  ValueError before any library call."""
+    _chk_dense(op, BF16, param.numel(), param=param, **bf16)
+    _chk_dense(op, torch.float32, param.numel(), **(f32 or {}))
+
+
 def adamw_step(param, grad, exp_avg, exp_avg_sq, clip_coef, lr, beta1, beta2, eps, weight_decay, step, zero_grad=True,
-               ema_shadow=None, ema_decay=0.0, background=0):
+               ema_shadow=None, ema_decay=0.0):
+    """All-bf16 state, torch's op sequence with a bf16 rounding after every op.  include/yat_hip.h yat_adamw_step."""
+    _chk_step("adamw_step", param, bf16=dict(grad=grad, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq, ema_shadow=ema_shadow))
     rc = _lib().yat_adamw_step(param.numel(), _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), _p(clip_coef), lr, beta1,
-                               beta2, eps, weight_decay, step, int(zero_grad), _p(ema_shadow), ema_decay, int(background),
-                               _stream())
+                               beta2, eps, weight_decay, step, int(zero_grad), _p(ema_shadow), ema_decay, _stream())
     _l.check(rc, "yat_adamw_step")
 
 
@@ -910,11 +918,8 @@ def adamw_master_step(param, master, grad, exp_avg, exp_avg_sq, clip_coef, lr, b
                       zero_grad=False, ema_shadow=None, ema_decay=0.0):
     """fp32 ``master`` / ``exp_avg`` / ``exp_avg_sq`` / ``ema_shadow`` updated in fp32 from the bf16 ``grad``; ``param`` (bf16)
     receives bf16(master).  include/yat_hip.h yat_adamw_master_step."""
-    _chk_bf16(param, grad)
-    f32 = (master, exp_avg, exp_avg_sq) + (() if ema_shadow is None else (ema_shadow,))
-    if any(t.dtype != torch.float32 or t.numel() != param.numel() or not t.is_contiguous() for t in f32) \
-            or grad.numel() != param.numel() or not (param.is_contiguous() and grad.is_contiguous()):
-        raise ValueError("adamw_master_step: fp32 contiguous master / moments / shadow of the parameters' size expected")
+    _chk_step("adamw_master_step", param, bf16=dict(grad=grad),
+              f32=dict(master=master, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq, ema_shadow=ema_shadow))
     rc = _lib().yat_adamw_master_step(param.numel(), _p(param), _p(master), _p(grad), _p(exp_avg), _p(exp_avg_sq),
                                       _p(clip_coef), lr, beta1, beta2, eps, weight_decay, step, int(zero_grad),
                                       _p(ema_shadow), ema_decay, _stream())
@@ -925,10 +930,7 @@ def adamw_sr_step(param, grad, exp_avg, exp_avg_sq, clip_coef, lr, beta1, beta2,
                   ema_shadow=None, ema_decay=0.0, seed=0, rng_step=0, elem_offset=0):
     """All-bf16 state updated in fp32 and stored with Philox stochastic rounding; ``elem_offset``: where ``param`` starts in the
     whole buffer (the random bits follow the global index).  include/yat_hip.h yat_adamw_sr_step."""
-    bf = (param, grad, exp_avg, exp_avg_sq) + (() if ema_shadow is None else (ema_shadow,))
-    _chk_bf16(*bf)
-    if any(t.numel() != param.numel() or not t.is_contiguous() for t in bf):
-        raise ValueError("adamw_sr_step: bf16 contiguous gradients / moments / shadow of the parameters' size expected")
+    _chk_step("adamw_sr_step", param, bf16=dict(grad=grad, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq, ema_shadow=ema_shadow))
     rc = _lib().yat_adamw_sr_step(param.numel(), _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), _p(clip_coef), lr, beta1,
                                   beta2, eps, weight_decay, step, int(zero_grad), _p(ema_shadow), ema_decay,
                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(rng_step), int(elem_offset), _stream())

@@ -32,6 +32,7 @@ replicas stay identical and the sharded step stays bit-identical to the replicat
 """
 from __future__ import annotations
 
+import bisect
 import os
 
 import torch
@@ -43,7 +44,7 @@ BF16 = torch.bfloat16
 
 NORM_CHUNK = 1 << 18        # elements per partial sum of the gradient norm (csrc/optim.hip NORM_CHUNK)
 NORM_PARTS = 8              # a bucket's pieces never straddle an eighth of it: shards of 1, 2, 4 or 8 ranks own whole pieces
-MASTER_GRID_PASS = 8192 * 256 * 8   # parameters one pass of yat_adamw_master_step's capped grid covers (csrc/optim.hip MASTER_MAX_BLOCKS)
+MASTER_GRID_PASS = 8192 * 256 * 8   # parameters one pass of the capped grid of all three steps covers (csrc/optim.hip STEP_MAX_BLOCKS)
 _OFF = ("", "0", "false", "no", "off")
 
 
@@ -72,7 +73,6 @@ def norm_pieces(seg_start, bucket_bounds, parts=NORM_PARTS):
             cuts.update(lo + k * (L // parts) for k in range(1, parts))
     cuts = sorted(cuts)
     piece_start, tensor_first = [], []
-    import bisect
     for t in range(len(seg) - 1):
         s0, s1 = seg[t], seg[t + 1]
         tensor_first.append(len(piece_start))
@@ -133,9 +133,6 @@ class FlatAdamW:
         # event per bucket; the next forward waits per bucket, so this HBM-bound pass hides under the forward GEMMs.
         # Anything else that reads parameters first calls model.join_pending_update().
         self.overlap_update = overlap_update and dev.type == "cuda"
-        # (yat_adamw_step's 48-VGPR background form -- a few persistent workgroups under the forward instead of the
-        # full-width kernel -- was measured and rejected in round 3; the update always uses the full-width kernel)
-        self.background_blocks = 0
         self._stream = None
 
     def _ema_decay_now(self):
@@ -175,32 +172,22 @@ class FlatAdamW:
             self.ema_steps += 1
             ema_decay = self._ema_decay_now()
 
-        bg = self.background_blocks if self.overlap_update else 0
-
         def update(lo, hi, step_count=None):
             # no gradient clear: every backward overwrites the whole flat gradient (accumulate_grads=False on the
             # first micro-step), like the reference's zero_grad(set_to_none=True) which writes nothing either
+            state = (m.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], coef, g["lr"], g["betas"][0], g["betas"][1],
+                     g["eps"], g["weight_decay"], self.step_count if step_count is None else step_count)
+            common = dict(zero_grad=False, ema_shadow=None if self.ema_shadow is None else self.ema_shadow[lo:hi],
+                          ema_decay=ema_decay)
             if self.master_weights:
-                ops.adamw_master_step(m.flat_param[lo:hi], self.master[lo:hi], m.flat_grad[lo:hi], self.exp_avg[lo:hi],
-                                      self.exp_avg_sq[lo:hi], coef, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
-                                      g["weight_decay"], self.step_count if step_count is None else step_count,
-                                      zero_grad=False, ema_shadow=None if self.ema_shadow is None else self.ema_shadow[lo:hi],
-                                      ema_decay=ema_decay)
-                return
-            if self.stochastic_rounding:
+                ops.adamw_master_step(m.flat_param[lo:hi], self.master[lo:hi], *state, **common)
+            elif self.stochastic_rounding:
                 # rng_step is the optimizer's own counter (a range's bias-correction step may repeat across steps); the bits
                 # follow the global index lo + i, so any slicing of the buffer into calls gives the same result
-                ops.adamw_sr_step(m.flat_param[lo:hi], m.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], coef,
-                                  g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
-                                  self.step_count if step_count is None else step_count, zero_grad=False,
-                                  ema_shadow=None if self.ema_shadow is None else self.ema_shadow[lo:hi], ema_decay=ema_decay,
-                                  seed=self.sr_seed, rng_step=self.step_count, elem_offset=lo)
-                return
-            ops.adamw_step(m.flat_param[lo:hi], m.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], coef,
-                           g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
-                           self.step_count if step_count is None else step_count,
-                           zero_grad=False, ema_shadow=None if self.ema_shadow is None else self.ema_shadow[lo:hi],
-                           ema_decay=ema_decay, background=bg)
+                ops.adamw_sr_step(m.flat_param[lo:hi], *state, **common, seed=self.sr_seed, rng_step=self.step_count,
+                                  elem_offset=lo)
+            else:
+                ops.adamw_step(m.flat_param[lo:hi], *state, **common)
 
         ranges = getattr(m, "update_ranges", None)
         if shard is not None:
@@ -224,15 +211,21 @@ class FlatAdamW:
             self._stream = compute_stream(m.flat_param.device, "opt")
         main = torch.cuda.current_stream()
         self._stream.wait_stream(main)
-        # one persistent event per bucket, re-recorded every step: the next forward's waits are then the same calls on
-        # the same objects step after step (a recorded launch plan can hold them)
-        if getattr(self, "_events", None) is None or len(self._events) != len(m.bucket_bounds):
-            self._events = [torch.cuda.Event() for _ in m.bucket_bounds]
+        events = self._ensure_events("_events", len(m.bucket_bounds))
         with torch.cuda.stream(self._stream):
-            for (lo, hi), ev in zip(m.bucket_bounds, self._events):
+            for (lo, hi), ev in zip(m.bucket_bounds, events):
                 update(lo, hi)
                 ev.record(self._stream)
-        m.param_events = self._events
+        m.param_events = events
+
+    def _ensure_events(self, name, n):
+        """One persistent event per bucket under ``self.<name>``, re-recorded every step: the next forward's waits are then the
+        same calls on the same objects step after step (a recorded launch plan can hold them)."""
+        events = getattr(self, name, None)
+        if events is None or len(events) != n:
+            events = [torch.cuda.Event() for _ in range(n)]
+            setattr(self, name, events)
+        return events
 
     # ------------------------------------------------------------------ sharded step
     def _shard(self):
@@ -270,21 +263,18 @@ class FlatAdamW:
             self._gather_stream = compute_stream(m.flat_param.device, "opt")
         upd, gat = self._stream, self._gather_stream
         upd.wait_stream(main)
-        nb = len(m.bucket_bounds)
-        if getattr(self, "_events", None) is None or len(self._events) != nb:
-            self._events = [torch.cuda.Event() for _ in range(nb)]
-        if getattr(self, "_upd_events", None) is None or len(self._upd_events) != nb:
-            self._upd_events = [torch.cuda.Event() for _ in range(nb)]
-        for i, (lo, hi) in enumerate(m.bucket_bounds):
+        events = self._ensure_events("_events", len(m.bucket_bounds))
+        upd_events = self._ensure_events("_upd_events", len(m.bucket_bounds))
+        for (lo, hi), ev, upd_ev in zip(m.bucket_bounds, events, upd_events):
             s_ = (hi - lo) // n
             with torch.cuda.stream(upd):
                 update(lo + r * s_, lo + (r + 1) * s_)
-                self._upd_events[i].record(upd)
+                upd_ev.record(upd)
             with torch.cuda.stream(gat):
-                gat.wait_event(self._upd_events[i])
+                gat.wait_event(upd_ev)
                 ddp.allgather_bulk(m.flat_param[lo:hi])
-                self._events[i].record(gat)
-        m.param_events = self._events
+                ev.record(gat)
+        m.param_events = events
 
     def gather_ema(self):
         """Sharded step: every rank's EMA shadow is current on its own slices only; before anybody reads the whole shadow
