@@ -511,6 +511,20 @@ int yat_adamw_sr_step(int64_t n, void* param, void* grad, void* exp_avg, void* e
                       double lr, double beta1, double beta2, double eps, double weight_decay, int step, int zero_grad,
                       void* ema_shadow, double ema_decay, uint64_t seed, int64_t rng_step, int64_t elem_offset,
                       yat_stream_t stream);
+/* A position-sensitive 64-bit fingerprint of a device buffer: the "same bits?" answer for a whole buffer in one streaming
+ * read (the checksum of a saved training state, yat_amd/common/trainer_state.py; safetensors carries none).  buf is read as
+ * n_words little-endian 32-bit words w_i.  With g = word_offset + i (64-bit) and x = (g << 32) ^ (g >> 32) ^ w_i the term is
+ * the splitmix64 finalizer of x + 0x9E3779B97F4A7C15:
+ *     z = x + 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *     t_i = z ^ (z >> 31)                                                          (all arithmetic mod 2^64)
+ * and out[0] = (accumulate ? out[0] : 0) + sum_i t_i mod 2^64.  Integer addition is associative and a term depends on
+ * (g, w_i) only, so the value depends neither on the grid nor on how the buffer is cut into calls: fp(whole) = sum of
+ * fp(slices), each slice called with word_offset = its first word's index in the whole (accumulate = 1 adds them up in
+ * place), by any rank in any order.  One launch (and an 8-byte memset when accumulate = 0): 16-byte loads per lane from the
+ * first 16-byte boundary, a grid capped at 2048 workgroups, one 64-bit atomic add per workgroup.  buf 4-byte aligned, out
+ * 8-byte aligned (a device pointer).  YAT_EINVAL before any launch for n_words <= 0, a NULL or misaligned buf or out. */
+int yat_fingerprint_u64(int64_t n_words, const void* buf, uint64_t word_offset, uint64_t* out, int accumulate,
+                        yat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ *
  * DC-AE decoder (diffusers AutoencoderDC, decoder only): the VAE decode of the validation images,

@@ -73,6 +73,10 @@ class SD15Model(Model):
             key = getattr(self.params, name, None)                     # the config key, else YAT_MASTER_WEIGHTS / YAT_STOCHASTIC_ROUNDING
             if key or (key is None and default()):
                 print(f"{name} is ignored: this recipe runs torch's own AdamW on the host, in the parameters' dtype")
+        for name in ("save_state", "resume_from"):                      # the resumable state is FlatAdamW's (common/trainer_state.py)
+            if getattr(self.params, name, None):
+                print(f"{name} is ignored: this recipe runs torch's own AdamW on the host and keeps no resumable trainer state")
+                setattr(self.params, name, None)
         return _TorchClipAdamW(trained, self.params.learning_rate, self.params.weight_decay)
 
     def extract_latents(self, images):

@@ -166,6 +166,20 @@ class AdapterSet:
         if self.grad_ready is not None:
             self.grad_ready(0)
 
+    # ---- the small host state a continued run needs beside the flat buffers (FlatAdamW.state_dict / load_state_dict)
+    def extra_state(self):
+        """JSON values: per entry the optimizer step count and the accumulation window's ``has_grad`` of a kind with module
+        dropout (``ModuleDropout.update_ranges``); a kind with more (LoRA's dropout counter) adds it."""
+        return dict(entries=[[e["module"], int(e["steps"]), bool(e["has_grad"])] for e in self.entries if "steps" in e])
+
+    def load_extra_state(self, state):
+        saved = {m: (s, h) for m, s, h in state.get("entries", [])}
+        for e in self.entries:
+            if "steps" in e:
+                if e["module"] not in saved:
+                    raise ValueError(f"adapter state: no step count for {e['module']}")
+                e["steps"], e["has_grad"] = int(saved[e["module"]][0]), bool(saved[e["module"]][1])
+
     # ---- checkpoint (peft layout: adapter_model.safetensors + adapter_config.json)
     @staticmethod
     def _peft_prefix(e):

@@ -36,6 +36,15 @@ import torch.distributed as dist
 from .shards import iter_legacy_cache, read_raw_shard, read_shard
 
 
+def _rng_to_json(st):
+    """``random.Random.getstate()`` as JSON values (version, the 625 words, the cached gauss value)."""
+    return [st[0], list(st[1]), st[2]]
+
+
+def _rng_from_json(st):
+    return (int(st[0]), tuple(int(x) for x in st[1]), st[2])
+
+
 class Batch:
     def __init__(self):
         self.embeddings = None
@@ -62,6 +71,9 @@ class BucketSampler:
         keys = list(model.aspect_ratios.keys()) if model is not None else []
         self.keys = [float(k) for k in keys]                      # table order = consensus priority order
         self.buckets = {k: deque() for k in self.keys}
+        # resumable position (state_dict / load_state_dict): per bucket item its (shard path, __key__), the stream position of
+        # the last element the CONSUMER took, and what a restore left for the stream to start from
+        self._refs, self._pos, self._resume, self._restore_cache = {}, None, None, {}
         self.legacy_cache_dir = legacy_cache_dir                  # cache/{idx}.npy tuples (common/cache.py) instead of shards
         if legacy_cache_dir:
             self.paths = []
@@ -76,7 +88,18 @@ class BucketSampler:
             raise FileNotFoundError("BucketSampler: no local shard found")
         self.paths = paths
 
-    def _shard_stream(self):
+    def _read(self, path):
+        """The samples of one shard in tar order, each tagged with the shard it came from (a restore hands over the shards it
+        has read already)."""
+        cached = self._restore_cache.pop(path, None)
+        for sample in (cached if cached is not None else self._read_shard(path)):
+            sample["__shard__"] = path
+            yield sample
+
+    def _read_shard(self, path):
+        return read_shard(path)
+
+    def _shard_stream(self, resume=None):
         rng = random.Random(self.seed + self.process_index)
         while self.legacy_cache_dir:
             samples = list(iter_legacy_cache(self.legacy_cache_dir, self.process_index, self.num_processes))
@@ -84,13 +107,31 @@ class BucketSampler:
                 raise FileNotFoundError(f"no cache/<idx>.npy sample for rank {self.process_index} in {self.legacy_cache_dir}")
             rng.shuffle(samples)
             yield from samples
+        order, start, skip = None, 0, 0
+        if resume is not None:
+            # the shard the consumer stood in is shuffled again from the generator state taken before its shuffle: the order
+            # inside it, the shards after it and every later epoch's order follow without replaying anything
+            order, start, skip = list(resume["order"]), int(resume["order_index"]), int(resume["consumed"])
+            rng.setstate(_rng_from_json(resume["rng"]))
         while True:
-            order = list(self.paths)
-            rng.shuffle(order)
-            for p in order:
-                samples = list(read_shard(p))
+            if order is None:
+                order, start = list(self.paths), 0
+                rng.shuffle(order)
+            for oi in range(start, len(order)):
+                cursor = dict(order=order, order_index=oi, rng=rng.getstate())     # shared by the shard's elements
+                samples = list(self._read(order[oi]))
                 rng.shuffle(samples)                               # webdataset .shuffle(1000) stand-in, seeded
-                yield from samples
+                for j in range(skip, len(samples)):
+                    samples[j]["__pos__"] = (cursor, j + 1)
+                    yield samples[j]
+                skip = 0
+            order = None
+
+    @staticmethod
+    def _stream_state(pos):
+        cursor, consumed = pos
+        return dict(order=list(cursor["order"]), order_index=cursor["order_index"], rng=_rng_to_json(cursor["rng"]),
+                    consumed=consumed)
 
     def _prefetched(self, stream):
         """``stream`` drained by a daemon producer thread through a bounded queue; exceptions travel to the consumer.  The
@@ -159,6 +200,23 @@ class BucketSampler:
         if "pooled.pt" in elem:                   # SD3.5 samples: (prompt_embeds, pooled_projections) travel together
             emb = (emb, elem["pooled.pt"])
         self.buckets[ratio].append((elem["latent.pt"], emb))
+        return ratio
+
+    def _make_item(self, elem):
+        """The bucket entry of a sample that a restore read again."""
+        emb = (elem["emb.pt"], elem["pooled.pt"]) if "pooled.pt" in elem else elem["emb.pt"]
+        return (elem["latent.pt"], emb)
+
+    def _ingest(self, elem):
+        """One element from the stream into its bucket; the consumer's position moves behind it."""
+        key = self.process_element(elem)
+        if key is not None and "__key__" in elem:
+            refs = self._refs.get(key)
+            if refs is None:
+                refs = self._refs[key] = deque(maxlen=self.buckets[key].maxlen)     # (a bounded bucket drops its oldest: so does this)
+            refs.append((elem.get("__shard__"), elem["__key__"]))
+        if "__pos__" in elem:
+            self._pos = elem.pop("__pos__")
 
     def _full_everywhere(self):
         counts = torch.tensor([len(self.buckets[k]) for k in self.keys], dtype=torch.int32)
@@ -171,22 +229,25 @@ class BucketSampler:
         return self.keys[int(full[0])] if full.numel() else None
 
     def __iter__(self):
-        stream = self._shard_stream()
+        stream = self._shard_stream(self._resume) if self._resume is not None else self._shard_stream()
         if self.decode_ahead > 0:
             stream = self._prefetched(stream)
         while True:
             # read ahead until this rank owns a full bucket (bounded), then ask everyone
             read = 0
             while not any(len(self.buckets[k]) >= self.batch_size for k in self.keys) and read < self.max_read_ahead:
-                self.process_element(next(stream))
+                self._ingest(next(stream))
                 read += 1
             key = self._full_everywhere()
             if key is None:
                 # some rank lacks this bucket: everybody ingests a few more samples and retries
                 for _ in range(self.batch_size):
-                    self.process_element(next(stream))
+                    self._ingest(next(stream))
                 continue
             items = [self.buckets[key].popleft() for _ in range(self.batch_size)]
+            if key in self._refs:
+                for _ in range(min(self.batch_size, len(self._refs[key]))):
+                    self._refs[key].popleft()
             yield self.make_batch(key, items)
 
     def make_batch(self, key, items):
@@ -195,6 +256,69 @@ class BucketSampler:
         batch.vae_features = torch.stack([it[0] for it in items])       # :161-162
         batch.embeddings = [it[1] for it in items]
         return batch
+
+    # ------------------------------------------------------------------ resumable position
+    def state_dict(self):
+        """The CONSUMER's position after the last batch it was handed, as JSON-able values: a sampler restored from it yields
+        exactly the batches the uninterrupted one goes on to yield, at any ``decode_ahead`` (what the producer thread has read
+        ahead but not handed over is not consumed).  Bucket entries are kept as (shard path, ``__key__``) references."""
+        if self.legacy_cache_dir:
+            raise NotImplementedError("the legacy cache/<idx>.npy path keeps no resumable position: use cached-feature shards")
+        for k in self.keys:
+            if len(self._refs.get(k, ())) != len(self.buckets[k]):
+                raise RuntimeError(f"bucket {k}: entries that did not come from the shard stream cannot be saved by reference")
+        stream = self._stream_state(self._pos) if self._pos is not None else self._resume
+        return dict(version=1, kind=type(self).__name__, seed=self.seed, process_index=self.process_index,
+                    num_processes=self.num_processes, batch_size=self.batch_size, keys=list(self.keys), stream=stream,
+                    buckets=[[k, [list(r) for r in self._refs.get(k, ())]] for k in self.keys])
+
+    def load_state_dict(self, state):
+        """Before the first batch is asked for.  Reads the shards that hold pending bucket entries and nothing else (the
+        stream reads the shard it stood in when it starts); never replays the run."""
+        if self.legacy_cache_dir:
+            raise NotImplementedError("the legacy cache/<idx>.npy path keeps no resumable position: use cached-feature shards")
+        if self._producer is not None or self._pos is not None:
+            raise RuntimeError("load_state_dict on a sampler that is already being read")
+        for name, mine in (("kind", type(self).__name__), ("seed", self.seed), ("process_index", self.process_index),
+                           ("num_processes", self.num_processes), ("batch_size", self.batch_size)):
+            if state.get(name) != mine:
+                raise ValueError(f"sampler state: {name} is {state.get(name)!r}, this sampler's is {mine!r}")
+        stream = state.get("stream")
+        wanted = {}
+        for refs in [refs for _, refs in state["buckets"]] + [self._extra_refs(state)]:
+            for path, key in refs:
+                wanted.setdefault(path, set()).add(key)
+        unknown = (set(wanted) | set(stream["order"] if stream else ())) - set(self.paths)
+        if unknown:
+            raise ValueError(f"sampler state: shard(s) not in this sampler's list: {sorted(unknown)[:3]}")
+        found, current = {}, (stream["order"][stream["order_index"]] if stream else None)
+        for path, keys in wanted.items():
+            samples = list(self._read_shard(path))
+            if path == current:
+                self._restore_cache[path] = samples            # (the stream starts in this shard: it is not read twice)
+            found.update({(path, s["__key__"]): s for s in samples if s["__key__"] in keys})
+        self.keys = [float(k) for k in state["keys"]]
+        self.buckets, self._refs = {}, {}
+        for k, refs in state["buckets"]:
+            k = float(k)
+            self.buckets[k], self._refs[k] = self._new_bucket(), self._new_bucket()
+            for path, key in refs:
+                if (path, key) not in found:
+                    raise ValueError(f"sampler state: sample {key!r} is not in {path}")
+                self.buckets[k].append(self._make_item(found[(path, key)]))
+                self._refs[k].append((path, key))
+        self._resume = stream
+        self._load_extra(state, found)
+
+    def _new_bucket(self):
+        return deque()
+
+    def _extra_refs(self, state):
+        """References to samples, beside the bucket entries, that a restore has to read again."""
+        return []
+
+    def _load_extra(self, state, found):
+        pass
 
 
 class BucketSamplerExtractFeatures(BucketSampler):
@@ -237,24 +361,81 @@ class BucketSamplerExtractFeatures(BucketSampler):
         self.text_encoder_max_batch_size = int(text_encoder_max_batch_size or batch_size)
         self.device_resize = bool(device_resize)
         self.generator = None
+        self._held_restored = []            # the shuffle buffer a restore decoded again, until the stream takes it over
 
-    def _shard_stream(self):
+    def _read_shard(self, path):
+        return read_raw_shard(path)
+
+    def _shard_stream(self, resume=None):
         rng = random.Random(self.seed + self.process_index)
-        held = []
+        held, order, start, skip, seen = [], None, 0, 0, 0
+        if resume is not None:
+            # the generator state behind the last draw, the samples read from the current shard so far and the shuffle buffer
+            # (decoded again by load_state_dict): everything the walk below depends on
+            order, start, skip, seen = list(resume["order"]), int(resume["order_index"]), int(resume["consumed"]), int(resume["seen"])
+            rng.setstate(_rng_from_json(resume["rng"]))
+            held, self._held_restored = self._held_restored, []
         while True:
-            order = list(self.paths)
-            rng.shuffle(order)
-            seen = 0
-            for p in order:
-                for sample in read_raw_shard(p):
+            if order is None:
+                order, start, seen = list(self.paths), 0, 0
+                rng.shuffle(order)
+            for oi in range(start, len(order)):
+                for n, sample in enumerate(self._read(order[oi])):
+                    if n < skip:
+                        continue
                     seen += 1
                     held.append(sample)
                     if len(held) > 2 * self.batch_size:
-                        yield held.pop(rng.randrange(len(held)))
+                        out = held.pop(rng.randrange(len(held)))
+                        out["__pos__"] = dict(order=order, order_index=oi, consumed=n + 1, seen=seen, rng=rng.getstate(),
+                                              held=[(h["__shard__"], h["__key__"]) for h in held])
+                        yield out
+                skip = 0
             if not seen:
                 raise FileNotFoundError(f"BucketSamplerExtractFeatures: no decodable image + caption sample in {self.paths}")
+            order = None
+
+    @staticmethod
+    def _stream_state(pos):
+        return dict(order=list(pos["order"]), order_index=pos["order_index"], consumed=pos["consumed"], seen=pos["seen"],
+                    rng=_rng_to_json(pos["rng"]), held=[list(r) for r in pos["held"]])
+
+    def state_dict(self):
+        """The base class's position plus the shuffle buffer (by reference, in ``stream``) and the state of the generator that
+        draws an AutoencoderKL latent's noise (hex bytes; None before the first batch)."""
+        state = super().state_dict()
+        gen = self.generator
+        state["generator"] = None if gen is None else bytes(gen.get_state().cpu().tolist()).hex()
+        return state
+
+    def _new_bucket(self):
+        return deque(maxlen=4 * self.batch_size)
+
+    def _extra_refs(self, state):
+        return [tuple(r) for r in (state.get("stream") or {}).get("held", [])]
+
+    def _load_extra(self, state, found):
+        self._held_restored = []
+        for path, key in self._extra_refs(state):
+            if (path, key) not in found:
+                raise ValueError(f"sampler state: sample {key!r} is not in {path}")
+            sample = found[(path, key)]
+            sample["__shard__"] = path
+            self._held_restored.append(sample)
+        if state.get("generator") is not None:
+            self.generator = torch.Generator(device=self.accelerator.device)
+            self.generator.set_state(torch.tensor(list(bytes.fromhex(state["generator"])), dtype=torch.uint8))
+
+    def _make_item(self, elem):
+        key, img = self._resized(elem)
+        return (img, elem["caption"])
 
     def process_element(self, elem):
+        key, img = self._resized(elem)
+        self.buckets[key].append((img, elem["caption"]))
+        return key
+
+    def _resized(self, elem):
         from ..extract_latents import find_closest_ratio
         from ..image import pillow_resize, resize_uint8
         img = torch.from_numpy(elem["image"])
@@ -265,7 +446,7 @@ class BucketSamplerExtractFeatures(BucketSampler):
             img = resize_uint8(img, th, tw, device=self.accelerator.device)
         else:
             img = pillow_resize(img, th, tw)
-        self.buckets[key].append((img, elem["caption"]))
+        return key, img
 
     def make_batch(self, key, items):
         if self.generator is None:

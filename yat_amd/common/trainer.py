@@ -192,7 +192,7 @@ def optimizer_arithmetic(optimizer):
     """One line for logs: which precision the optimizer state in force is kept and updated in (yat_amd/optim.py)."""
     if getattr(optimizer, "master_weights", False):
         return ("master_weights (fp32 master weights, moments and EMA shadow updated in fp32; the bf16 parameters are their "
-                "rounding; not the reference's arithmetic, fp32 state is not checkpointed)")
+                "rounding; not the reference's arithmetic; the fp32 state is saved with save_state only)")
     if getattr(optimizer, "stochastic_rounding", False):
         return ("stochastic_rounding (parameters, moments and EMA shadow in bf16; the update is computed in fp32 from the bf16 "
                 "state and every stored value is Philox-rounded up or down, unbiased; not the reference's arithmetic)")
@@ -458,6 +458,15 @@ class Model:
         if getattr(p, "warmup_steps", None) is not None:
             self.lr_scheduler = WarmupLR(self.optimizer, p.warmup_steps)
         self.ema_model = self.optimizer.ema_shadow
+        # `resume_from` (extension, common/trainer_state.py): optimizer, scheduler, sampler and the RNGs go back to where the
+        # run stood after the save of step K; the restored master weights are the truth (no resync_master behind this)
+        if getattr(p, "resume_from", None):
+            from . import trainer_state
+            found = trainer_state.resolve(p.resume_from)
+            if found is None:
+                print("resume_from: latest -- no models/<step> with a complete trainer state here: a fresh start")
+            else:
+                trainer_state.load(self, found)
 
     # ---- :298-403
     def run(self, max_steps=None, on_step=None):
@@ -581,6 +590,11 @@ class Model:
                 self.save_model()
                 if stored is not None:
                     trained.flat_param.copy_(stored)
+            if getattr(self.params, "save_state", False):
+                # (extension) after validate() and save_model() and with the trained weights back in place: the point from
+                # which the uninterrupted run goes on -- every rank takes part (common/trainer_state.py)
+                from . import trainer_state
+                trainer_state.save(self)
 
 
 class WarmupLR:

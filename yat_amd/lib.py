@@ -114,6 +114,7 @@ SIGNATURES = {
     "yat_adamw_step": (I, [I64, P, P, P, P, P, D, D, D, D, D, I, I, P, D, P]),
     "yat_adamw_master_step": (I, [I64, P, P, P, P, P, P, D, D, D, D, D, I, I, P, D, P]),
     "yat_adamw_sr_step": (I, [I64, P, P, P, P, P, D, D, D, D, D, I, I, P, D, U64, I64, I64, P]),
+    "yat_fingerprint_u64": (I, [I64, P, U64, P, I, P]),
     "yat_dcae_conv3x3": (I, [I, I, I, I, I, I, I, P, P, P, I, P, I, P, I, P, P]),
     "yat_dcae_msla_aggregate": (I, [I, I, I, I, P, P, P, P, P]),
     "yat_dcae_rmsnorm_bias": (I, [I, I, F, P, P, P, P, I, P, P]),

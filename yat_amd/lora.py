@@ -95,6 +95,13 @@ class LoRAAdapters(AdapterSet):
         self._drop = self.dropout if (training and self.dropout > 0.0) else 0.0
         self._step += 1
 
+    def extra_state(self):
+        return dict(super().extra_state(), dropout_step=int(self._step))       # the counter the mask seeds are derived from
+
+    def load_extra_state(self, state):
+        super().load_extra_state(state)
+        self._step = int(state["dropout_step"])
+
     def _mask_seed(self, e):
         return (self._seed * 1000003 + self._step) * 4096 + e["index"]
 

@@ -937,6 +937,31 @@ def adamw_sr_step(param, grad, exp_avg, exp_avg_sq, clip_coef, lr, beta1, beta2,
     _l.check(rc, "yat_adamw_sr_step")
 
 
+def fingerprint(t, word_offset=0, out=None, accumulate=False):
+    """The position-sensitive 64-bit fingerprint of ``t``'s bytes read as 32-bit words, the first of them at index
+    ``word_offset`` of the whole (include/yat_hip.h yat_fingerprint_u64): fp(whole) = the sum mod 2^64 of fp(slices).  Without
+    ``out`` -> a Python int in [0, 2^64) (one 8-byte device->host copy); with ``out`` (one int64 on the device) the value is
+    written there -- added to what it holds with ``accumulate`` -- and nothing syncs.  ValueError before any library call for a
+    strided tensor, a byte length that is not a multiple of 4 or a pointer that is not 4-byte aligned."""
+    if not torch.is_tensor(t) or not t.is_contiguous():
+        raise ValueError("fingerprint: a contiguous (unstrided) tensor only")
+    nbytes = t.numel() * t.element_size()
+    if nbytes == 0 or nbytes % 4:
+        raise ValueError(f"fingerprint: {nbytes} bytes is not a positive multiple of 4")
+    if t.is_cuda and t.data_ptr() % 4:
+        raise ValueError("fingerprint: the buffer must be 4-byte aligned")
+    if not 0 <= int(word_offset) < 1 << 64:
+        raise ValueError("fingerprint: word_offset must fit 64 unsigned bits")
+    if out is not None and (out.dtype != torch.int64 or out.numel() != 1 or out.device != t.device):
+        raise ValueError("fingerprint: out is one int64 on the buffer's device")
+    if accumulate and out is None:
+        raise ValueError("fingerprint: accumulate needs out")
+    dst = torch.empty(1, dtype=torch.int64, device=t.device) if out is None else out
+    rc = _lib().yat_fingerprint_u64(nbytes // 4, _p(t), int(word_offset), _p(dst), int(bool(accumulate)), _stream())
+    _l.check(rc, "yat_fingerprint_u64")
+    return dst if out is not None else int(dst.item()) & 0xFFFFFFFFFFFFFFFF
+
+
 # ----------------------------------------------------------------------------------------------- DC-AE decoder (yat_amd/dcae.py)
 def dcae_conv3x3(x, w, y, B, H, W, Cin, Cout, bias=None, upsample=False, silu=False, shortcut_mode=0, shortcut=None,
                  shortcut_channels=0, residual=None, out_nchw=False):

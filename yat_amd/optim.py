@@ -17,13 +17,14 @@ an extension of this package, not a restatement of the reference.  At the recipe
 update is a fraction of a bf16 ulp of most weights, so the all-bf16 step above leaves them bitwise where they were.  With
 master weights the step keeps an fp32 copy of every trained parameter, fp32 moments and an fp32 EMA shadow (12 B / parameter
 more, 16 with EMA) and yat_adamw_master_step writes the bf16 flat buffer -- still what every forward and backward kernel
-reads -- as bf16(master).  Gradients, the gradient norm and the clip coefficient stay exactly as they are.  The fp32 state is
-not checkpointed: a restarted run re-derives its master from the bf16 weights it loads.  The sharded step is refused.
+reads -- as bf16(master).  Gradients, the gradient norm and the clip coefficient stay exactly as they are.  The fp32 state
+travels with ``state_dict()`` (the resumable trainer state, common/trainer_state.py); a run started from the weights alone
+re-derives its master from the bf16 weights it loads.  The sharded step is refused.
 
 Stochastic rounding (``FlatAdamW(stochastic_rounding=True, sr_seed=...)``, ``YAT_STOCHASTIC_ROUNDING=1``, config key
 ``stochastic_rounding``; off by default, and refused together with master weights): the other answer to the same stall, also an
-extension.  The state stays bf16 -- no master copy, no extra bytes, nothing more to checkpoint -- and yat_adamw_sr_step computes
-the update in fp32 from it and rounds every stored parameter, moment and shadow value up or down with the probability of its
+extension.  The state stays bf16 -- no master copy, no extra bytes, no tensor beyond the bf16 state to checkpoint (the step
+count that keys the bits is in ``state_dict()``) -- and yat_adamw_sr_step computes the update in fp32 from it and rounds every stored parameter, moment and shadow value up or down with the probability of its
 fractional position between the two bf16 neighbours, so the stored value is unbiased: sub-ulp updates, the 1e-3 decay of
 ``exp_avg_sq`` and the shadow's 1e-3 pull accumulate in expectation.  The random bits are Philox4x32 of (``sr_seed``, the
 optimizer's step count, the parameter's index in the flat buffer, the field) and of nothing else: every way this class slices
@@ -94,6 +95,32 @@ def norm_pieces(seg_start, bucket_bounds, parts=NORM_PARTS):
         chunk_base.append(chunk_base[-1] + n)
         mx = max(mx, n)
     return piece_start, tensor_first, chunk_base, mx, part_of
+
+
+def trained_layout(trained):
+    """What a saved optimizer state is tied to: one string per tensor of the trained object (a model: name, shape and offset in
+    the flat buffer; an adapter set: kind, rank, padded rank and target list, then every entry's module, extents and span) and
+    the norm segments and total.  ``layout_sha256`` is the fingerprint of the list; the list itself names what differs."""
+    out = []
+    if hasattr(trained, "entries"):
+        out.append(f"adapter kind={trained.kind} r={getattr(trained, 'r', None)} R={getattr(trained, 'R', None)} "
+                   f"targets={sorted(trained.targets)}")
+        for e in trained.entries:
+            out.append(f"{e['module']} out={e['out']} in={e['inn']} span={tuple(e['span']) if 'span' in e else None}")
+        for k, v in trained.state_dict().items():
+            out.append(f"{k} {tuple(v.shape)}")
+    else:
+        base, size = trained.flat_param.data_ptr(), trained.flat_param.element_size()
+        for k, v in trained.P.items():
+            out.append(f"{k} {tuple(v.shape)} @{(v.data_ptr() - base) // size}")
+    out.append(f"seg_start={[int(x) for x in trained.seg_start.tolist()]}")
+    out.append(f"numel_flat={int(trained.numel_flat)}")
+    return out
+
+
+def layout_sha256(layout):
+    import hashlib
+    return hashlib.sha256("\n".join(layout).encode()).hexdigest()
 
 
 class FlatAdamW:
@@ -287,6 +314,88 @@ class FlatAdamW:
         for lo, hi in self.model.bucket_bounds:
             shard.ddp.allgather_bulk(self.ema_shadow[lo:hi])
         return True
+
+    # ------------------------------------------------------------------ resumable state
+    @property
+    def mode(self):
+        return "master" if self.master_weights else ("sr" if self.stochastic_rounding else "bf16")
+
+    def _state_tensors(self):
+        t = dict(param=self.model.flat_param, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq)
+        if self.ema_shadow is not None:
+            t["ema_shadow"] = self.ema_shadow
+        if self.master is not None:
+            t["master"] = self.master
+        return t
+
+    def state_dict(self):
+        """Everything a continued run needs from this optimizer, bit for bit: ``tensors`` (the device buffers themselves, flat and
+        in their own dtypes: the trained ``param``, ``exp_avg``, ``exp_avg_sq``, ``ema_shadow`` and ``master`` where present),
+        ``scalars`` (JSON values) and ``layout`` (the entries ``layout_sha256`` is taken over).  Refused under the sharded
+        optimizer step, where the moments are current on a rank's own slices only."""
+        if self._shard() is not None:
+            raise NotImplementedError("state_dict with a sharded optimizer step (shard_optimizer / YAT_SHARD_OPTIMIZER) is not "
+                                      "built: the moments are current on each rank's own slices only")
+        self.model.join_pending_update()
+        g = self.param_groups[0]
+        layout = trained_layout(self.model)
+        scalars = dict(mode=self.mode, sr_seed=self.sr_seed, step_count=self.step_count, ema_steps=self.ema_steps,
+                       ema_decay=self.ema_decay, use_ema=self.ema_shadow is not None, max_grad_norm=self.max_grad_norm,
+                       param_groups=[dict(lr=g["lr"], initial_lr=g["initial_lr"], weight_decay=g["weight_decay"],
+                                          betas=list(g["betas"]), eps=g["eps"])],
+                       layout_sha256=layout_sha256(layout))
+        hook = getattr(self.model, "extra_state", None)
+        if hook is not None:
+            scalars["adapter_state"] = hook()
+        return dict(tensors=self._state_tensors(), scalars=scalars, layout=layout)
+
+    def load_state_dict(self, state):
+        """Refuses (ValueError) another layout -- naming the first differing entry --, another mode (a bf16-state checkpoint does
+        not silently become a master-weights run: ``pretrained_model_path`` is the way to start a new run from old weights),
+        another ``sr_seed`` or EMA setting and, with master weights, a ``param`` that is not bitwise bf16(master).  Nothing is
+        written before every check has passed."""
+        if self._shard() is not None:
+            raise NotImplementedError("load_state_dict with a sharded optimizer step is not built")
+        self.model.join_pending_update()
+        sc, tensors = state["scalars"], state["tensors"]
+        mine = trained_layout(self.model)
+        if sc.get("layout_sha256") != layout_sha256(mine):
+            theirs = state.get("layout")
+            if theirs is None:
+                raise ValueError("optimizer state: it was saved from another layout of the trained parameters")
+            for i in range(max(len(mine), len(theirs))):
+                a, b = (mine[i] if i < len(mine) else None), (theirs[i] if i < len(theirs) else None)
+                if a != b:
+                    raise ValueError(f"optimizer state: another layout of the trained parameters; entry {i} is {b!r} in the "
+                                     f"state and {a!r} here")
+            raise ValueError("optimizer state: the layout fingerprint does not belong to the layout stored with it")
+        if sc["mode"] != self.mode:
+            raise ValueError(f"optimizer state: it was saved in mode {sc['mode']!r} and this optimizer runs in {self.mode!r}; "
+                             "modes are not converted (start a new run from the weights with pretrained_model_path)")
+        if int(sc["sr_seed"]) != self.sr_seed:
+            raise ValueError(f"optimizer state: sr_seed {sc['sr_seed']} in the state, {self.sr_seed} here")
+        if bool(sc["use_ema"]) != (self.ema_shadow is not None):
+            raise ValueError(f"optimizer state: use_ema is {bool(sc['use_ema'])} in the state and {self.ema_shadow is not None} here")
+        dst = self._state_tensors()
+        if set(tensors) != set(dst):
+            raise ValueError(f"optimizer state: tensors {sorted(tensors)} in the state, {sorted(dst)} here")
+        for name, t in dst.items():
+            s = tensors[name]
+            if s.dtype != t.dtype or s.numel() != t.numel() or s.dim() != 1:
+                raise ValueError(f"optimizer state: {name} is {s.dtype} {tuple(s.shape)}, expected {t.dtype} {tuple(t.shape)}")
+        if self.master is not None:
+            p, m = tensors["param"], tensors["master"]
+            if not torch.equal(p.view(torch.int16).cpu(), m.to(BF16).view(torch.int16).cpu()):
+                raise ValueError("optimizer state: param is not bitwise bf16(master)")
+        for name, t in dst.items():
+            t.copy_(tensors[name])
+        g, sg = self.param_groups[0], sc["param_groups"][0]
+        g.update(lr=float(sg["lr"]), initial_lr=float(sg["initial_lr"]), weight_decay=float(sg["weight_decay"]),
+                 betas=tuple(float(b) for b in sg["betas"]), eps=float(sg["eps"]))
+        self.step_count, self.ema_steps, self.ema_decay = int(sc["step_count"]), int(sc["ema_steps"]), float(sc["ema_decay"])
+        hook = getattr(self.model, "load_extra_state", None)
+        if hook is not None:
+            hook(sc.get("adapter_state") or {})
 
     def zero_grad(self, set_to_none=False):
         # the gradient clear is fused into step(); explicit calls (e.g. before the first step) still work
