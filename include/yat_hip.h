@@ -91,7 +91,7 @@ uint64_t yat_gemm_epilogue_size(void);   /* sizeof(yat_gemm_epilogue) in this bu
 int yat_gemm_bf16(int a_t, int b_t, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
                   void* C, int ldc, const yat_gemm_epilogue* ep, yat_stream_t stream);
 
-/* Same, with an optional split-K workspace and a per-call POLICY WORD `variant` = v + 100*s + 10000*c:
+/* Same, with an optional split-K workspace and a per-call POLICY WORD `variant` = v + 100*s + 10000*c + 1000000*g:
  *   v  tile variant: 0 = automatic policy, 1 = 128x128 tile, 4 = 256x256 tile, 5 = 256x320 tile (two staggered wave
  *      groups, gemm256.hip);
  *   s  0 = the policy decides; 1..32 forces that split-K factor on variant 4 or 5 (tests / tuning);
@@ -102,6 +102,10 @@ int yat_gemm_bf16(int a_t, int b_t, int M, int N, int K, const void* A, int lda,
  *      travels with the call -- the library keeps no policy state -- and changes tile / split choice only, i.e. the
  *      summation order of the result, never its meaning.  No reference counterpart (torch picks its GEMM algorithms per
  *      call, unaware of the caller's streams).
+ *   g  0 = the policy decides; 1..64 forces the tile order of the 256-row kernels: that many rows of 256-row tiles form
+ *      one group that walks the column tiles together (tuning: scripts/gemm_group_sweep.py; ignored by the 128x128 tile).
+ *      The policy's own choice is 8 for the dgrad layout with K >= 8192, else the kernel's default of 4.  Tile order
+ *      changes which tiles run side by side, never a result bit.
  * workspace (fp32, >= ksplit*M*N*4 bytes) lets the policy split K for shapes that leave CUs idle (small outputs with a
  * long reduction: weight gradients); with workspace == NULL K is never split. */
 int yat_gemm_bf16_ex(int a_t, int b_t, int M, int N, int K, const void* A, int lda, const void* B, int ldb,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Bit-identity of two builds of the GEMM kernels: prints one SHA-1 per (layout, tile variant, K split, shape) of the output of
-seeded inputs.  Run once per build (YAT_HIP_LIB selects it) and diff the two listings:
+seeded inputs, and per (layout, shape) of what the automatic policy (variant 0) gives with one and with two GEMM streams.  Run once per build (YAT_HIP_LIB selects it) and diff the two listings:
 
     python scripts/gemm_hash.py > a.txt;  YAT_HIP_LIB=yat_amd/build/variants/libyat_X.so python scripts/gemm_hash.py > b.txt
 
@@ -43,6 +43,19 @@ def main():
                 ok = err < 4e-3
                 bad += not ok
                 print(f"{lay} v{variant:3d} {m:5d}x{n:5d}x{k:5d} {sha(out)} rel {err:.2e}{'' if ok else '  <-- WRONG'}", flush=True)
+            # the automatic path (variant 0): what the host policy picks alone on the chip and beside a second GEMM stream
+            try:
+                for streams in (1, 2):
+                    ops.gemm_concurrency(streams)
+                    out = torch.full((m, n), float("nan"), dtype=BF, device=dev)
+                    ops.gemm(a, b, out, a_t=a_t, b_t=b_t, M=m, N=n, K=k, variant=0)
+                    torch.cuda.synchronize()
+                    err = ((out.float() - ref).norm() / ref.norm()).item()
+                    ok = err < 4e-3
+                    bad += not ok
+                    print(f"{lay} policy c{streams} {m:5d}x{n:5d}x{k:5d} {sha(out)} rel {err:.2e}{'' if ok else '  <-- WRONG'}", flush=True)
+            finally:
+                ops.gemm_concurrency(1)
     # fused epilogues on the k-strided-B layouts
     m, hc, d = 2048, 5600, 2240
     dy = (torch.randn(m, d, device=dev, generator=g) * 0.5).to(BF)

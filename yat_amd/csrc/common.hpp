@@ -21,10 +21,8 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 #include <stdlib.h>
 #ifdef YAT_TUNING
 #define YAT_TUNE_INT(name, dflt) (getenv(name) ? atoi(getenv(name)) : (dflt))
-#define YAT_TUNE_F64(name, dflt) (getenv(name) ? atof(getenv(name)) : (dflt))
 #else
 #define YAT_TUNE_INT(name, dflt) (dflt)
-#define YAT_TUNE_F64(name, dflt) (dflt)
 #endif
 
 #define YAT_CHECK_LAUNCH()                                  \

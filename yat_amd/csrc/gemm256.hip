@@ -157,9 +157,9 @@ __device__ __forceinline__ int xcd_contiguous(int nwg) {
 }
 
 // One workgroup's whole job: `id` = work item inside problem p (tile x K slice, before the row-group swizzle).
-template <bool A_T, bool B_T, int NT, int EPI = 0>      // EPI: 0 standard, 1 GLU backward, 2 standard + pre_add, 3 act backward,
-                                                         //      4 standard + row sums of A (wgrad + bias gradient),
-                                                         //      5 standard, second operand pair behind K (forward layout)
+// EPI: the epilogue class, a GemmEpi (gemm_policy.hpp): plain | GLU backward | plain + pre_add | activation backward |
+// plain + row sums of A (wgrad + bias gradient) | plain, second operand pair behind K (forward layout)
+template <bool A_T, bool B_T, int NT, int EPI = EPI_PLAIN>
 __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
     using G = Geo<NT>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -182,14 +182,14 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
     // EPI 5, the second operand pair (C = epilogue(A B^T + A2 B2^T): a PEFT adapter's factored term T P^T folded into the base
     // Linear): A2 / B2 have the row strides of A / B, so the K2 / 64 k-tiles behind the last tile of K are the same per-lane
     // offsets against two other buffer resources -- nothing else in the loop knows.  Column tiles of one A2 block: a2_group.
-    const int a2_col = (EPI == 5 && p.a2_group > 0) ? (n0 / p.a2_group) * p.K2 : 0;
-    const __amdgpu_buffer_rsrc_t ra2 = make_rsrc(EPI == 5 ? p.A2 + a2_col : p.A, EPI == 5 ? p.a2_bytes - (uint64_t)a2_col * 2 : 0);
-    const __amdgpu_buffer_rsrc_t rb2 = make_rsrc(EPI == 5 ? p.B2 : p.B, EPI == 5 ? p.b2_bytes : 0);
+    const int a2_col = (EPI == EPI_PAIR2 && p.a2_group > 0) ? (n0 / p.a2_group) * p.K2 : 0;
+    const __amdgpu_buffer_rsrc_t ra2 = make_rsrc(EPI == EPI_PAIR2 ? p.A2 + a2_col : p.A, EPI == EPI_PAIR2 ? p.a2_bytes - (uint64_t)a2_col * 2 : 0);
+    const __amdgpu_buffer_rsrc_t rb2 = make_rsrc(EPI == EPI_PAIR2 ? p.B2 : p.B, EPI == EPI_PAIR2 ? p.b2_bytes : 0);
 
     const uint32_t a_kstep = A_T ? (uint32_t)(BK * p.lda * 2) : (uint32_t)(BK * 2);
     const uint32_t b_kstep = B_T ? (uint32_t)(BK * p.ldb * 2) : (uint32_t)(BK * 2);
     const int nt_main = (p.K + BK - 1) / BK;
-    const int nt_all = nt_main + (EPI == 5 ? p.K2 / BK : 0);
+    const int nt_all = nt_main + (EPI == EPI_PAIR2 ? p.K2 / BK : 0);
     const int kt0 = (int)(((int64_t)nt_all * ksl) / p.ksplit);                 // this slice: k-tiles [kt0, kt0 + nt)
     const int nt = (int)(((int64_t)nt_all * (ksl + 1)) / p.ksplit) - kt0;
     const bool ragged = (p.K & (BK - 1)) != 0;
@@ -220,9 +220,9 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
     // EPI 4: the bias gradient of the Linear whose weight gradient this is = row sums of A (= dy^T) over K, from one extra MFMA
     // per A fragment against a fragment of ones -- in the waves that own column slice 0 of the FIRST column tile only (every
     // column tile sees the same A panel).  All 16 result columns of such a tile are equal; column 0 is stored.
-    const bool rs_wave = EPI == 4 && p.rowsum != nullptr && tn == 0 && wc == 0;
-    f32x4 racc[EPI == 4 ? 8 : 1];
-    if (EPI == 4) {
+    const bool rs_wave = EPI == EPI_ROWSUM && p.rowsum != nullptr && tn == 0 && wc == 0;
+    f32x4 racc[EPI == EPI_ROWSUM ? 8 : 1];
+    if (EPI == EPI_ROWSUM) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) racc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
@@ -334,7 +334,7 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
         auto dma = [&](auto checked, bool is_a, int pi, uint32_t voff, uint32_t delta, int tl, int kh_half = 0) {
             constexpr bool CHECKED = decltype(checked)::value;
             const int tg = ktile(tl);
-            const bool second = EPI == 5 && tg >= nt_main;                  // uniform: a tile of the second operand pair
+            const bool second = EPI == EPI_PAIR2 && tg >= nt_main;                  // uniform: a tile of the second operand pair
             const int t = second ? tg - nt_main : tg;
             YAT_LDS void* dst = (YAT_LDS void*)(smem + (tl & 1) * G::STAGE + (is_a ? 0 : G::A_BYTES) + pi * 1024);
             const uint32_t soff = (uint32_t)t * (is_a ? a_kstep : b_kstep) + delta;
@@ -408,7 +408,7 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
                         batch_piece(kk_c, fast_c, t, idx / GAP);
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                    if (EPI == 4 && idx == 8 * NT - 1 && rs_wave) {
+                    if (EPI == EPI_ROWSUM && idx == 8 * NT - 1 && rs_wave) {
                         bf16x8 ones;
 #pragma unroll
                         for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
@@ -479,7 +479,7 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
     else k_loop(std::integral_constant<int, 1>{});
     if (grp == 0) YAT_PHASE_BARRIER();         // pair group 1's last barrier
 
-    if (EPI == 4 && rs_wave && p.ksplit == 1 && (lane >> 4) == 0) {
+    if (EPI == EPI_ROWSUM && rs_wave && p.ksplit == 1 && (lane >> 4) == 0) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int m = m0 + grp * 128 + i * 16 + lane;
@@ -514,10 +514,10 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
         // four passes of a tile paid an HBM round trip behind its slab round trip (the gated-residual and GLU-backward GEMMs
         // ran 714 .. 990 TFLOP/s in the step).  Same loads, same arithmetic, same stores: bit-identical.
         constexpr int UPL = (32 * CPR + 63) / 64;          // 8-column units per lane and pass
-        const bool pre_on = !split && (EPI == 1 || EPI == 3 || EPI == 2 || p.res != nullptr);
+        const bool pre_on = !split && (EPI == EPI_GLU_BWD || EPI == EPI_ACT_BWD || EPI == EPI_PRE_ADD || p.res != nullptr);
         // one input stream (residual | z): a whole pass ahead, double-buffered; two streams (GLU u_a + u_g, residual + pre_add):
         // the registers do not hold two passes of both -- loaded at the top of their own pass, before its slab round trip
-        constexpr bool AHEAD = EPI != 1 && EPI != 2;
+        constexpr bool AHEAD = EPI != EPI_GLU_BWD && EPI != EPI_PRE_ADD;
         EpiIn ein[AHEAD ? 2 : 1][UPL];
         auto unit = [&](int pass, int k, int& row, int& ch, int& m, int& n) {
             const int u = lane + 64 * k;
@@ -532,15 +532,15 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
             for (int k = 0; k < UPL; ++k) {
                 int row, ch, m, n;
                 if (!unit(pass, k, row, ch, m, n)) continue;
-                if (EPI == 1) {
+                if (EPI == EPI_GLU_BWD) {
                     const bf16_t* up = p.glu_u + (int64_t)m * p.ld_glu + n;
                     in[k].a = *reinterpret_cast<const u32x4*>(up);
                     in[k].b = *reinterpret_cast<const u32x4*>(up + p.N);
-                } else if (EPI == 3) {
+                } else if (EPI == EPI_ACT_BWD) {
                     in[k].a = *reinterpret_cast<const u32x4*>(p.dact_z + (int64_t)m * p.ld_z + n);
                 } else {
                     if (p.res) in[k].a = *reinterpret_cast<const u32x4*>(p.res + (int64_t)m * p.ldr + n);
-                    if (EPI == 2) in[k].b = *reinterpret_cast<const u32x4*>(p.pre_add + (int64_t)m * p.ld_pre + n);
+                    if (EPI == EPI_PRE_ADD) in[k].b = *reinterpret_cast<const u32x4*>(p.pre_add + (int64_t)m * p.ld_pre + n);
                 }
             }
         };
@@ -569,9 +569,9 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
                     } else {
                         float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                         const EpiIn* pin = pre_on ? &ein[AHEAD ? (pass & 1) : 0][k] : nullptr;
-                        if (EPI == 1) glu_bwd_store<8>(p, v, m, n, pin);
-                        else if (EPI == 3) act_bwd_store<8>(p, v, m, n, pin);
-                        else gemm_epilogue_store8<EPI == 2, A_T && B_T>(p, v, m, n, m / rpb, pin);     // (weight-gradient layout: non-temporal result)
+                        if (EPI == EPI_GLU_BWD) glu_bwd_store<8>(p, v, m, n, pin);
+                        else if (EPI == EPI_ACT_BWD) act_bwd_store<8>(p, v, m, n, pin);
+                        else gemm_epilogue_store8<EPI == EPI_PRE_ADD, A_T && B_T>(p, v, m, n, m / rpb, pin);     // (weight-gradient layout: non-temporal result)
                     }
                 }
             }
@@ -588,12 +588,12 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
         for (int j = 0; j < NT; ++j) {
             const int n = n0 + wc * 16 * NT + j * 16 + 4 * (lane >> 4);
             if (n >= p.N) continue;
-            if (EPI == 1 || EPI == 3) {
+            if (EPI == EPI_GLU_BWD || EPI == EPI_ACT_BWD) {
                 const float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-                if (EPI == 1) glu_bwd_store<4>(p, v, m, n);
+                if (EPI == EPI_GLU_BWD) glu_bwd_store<4>(p, v, m, n);
                 else act_bwd_store<4>(p, v, m, n);
             } else {
-                gemm_epilogue_store<EPI == 2>(p, acc[i][j], m, n, b);
+                gemm_epilogue_store<EPI == EPI_PRE_ADD>(p, acc[i][j], m, n, b);
             }
         }
     }
@@ -605,7 +605,7 @@ __device__ __forceinline__ void gemm256_body(const GemmP p, int id) {
 // K sweep it came with puts the fixed cost of a tile round at 6.6 us against 1.75 us per K-tile -- the time is in the loop,
 // not between tiles.  Delaying the first round's workgroups so that the epilogues leave lockstep changes nothing (the
 // epilogue is not HBM-bound: cold outputs cost nothing).
-template <bool A_T, bool B_T, int NT, int EPI = 0>
+template <bool A_T, bool B_T, int NT, int EPI = EPI_PLAIN>
 __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmP p) {
     gemm256_body<A_T, B_T, NT, EPI>(p, xcd_contiguous(p.nbm * p.nbn * p.ksplit));
 }
@@ -627,7 +627,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_grouped_kernel(GroupedP gp) {
     int g = 0;
     while (g + 1 < gp.ngroups && id >= gp.first[g + 1]) ++g;
     // the weight-gradient layout carries the row sums of A (bias gradients) for the problems that ask for them
-    gemm256_body<A_T, B_T, NT, (A_T && B_T && NT == 4) ? 4 : 0>(gp.g[g], id - gp.first[g]);
+    gemm256_body<A_T, B_T, NT, (A_T && B_T && NT == 4) ? EPI_ROWSUM : EPI_PLAIN>(gp.g[g], id - gp.first[g]);
 }
 
 template <bool A_T, bool B_T, int NT>
@@ -660,7 +660,7 @@ int launch256_grouped(int ngroups, const GemmP* probs, hipStream_t stream) {
 // (gemm1w -- the same 256 x 256 x 64 tile with ONE wave per SIMD and the K loop software-pipelined inside each wave, tile
 // variant 6 -- was measured in round 2, never won a shape and is gone; profiles/LOG_r01_r03.md section 9.)
 
-template <bool A_T, bool B_T, int NT, int EPI = 0>
+template <bool A_T, bool B_T, int NT, int EPI = EPI_PLAIN>
 int launch256(const GemmP& p0, hipStream_t stream) {
     using G = Geo<NT>;
     GemmP p = p0;
@@ -721,34 +721,20 @@ int yat_gemm256_grouped_launch(int a_t, int b_t, int ngroups, const GemmP* probs
 
 // variant: 4 -> BN=256, 5 -> BN=320.  (A 256 x 192 tile -- no ragged column tile at N = 1152 / 3456 / 4608 -- was
 // instantiated and measured at the PixArt shapes: never faster than the policy's pick, 5-25 % slower than BN=320; removed.)
-int yat_gemm256_launch(int a_t, int b_t, int nt_variant, const GemmP& p, hipStream_t stream) {
-    if (p.glu_u) {                 // GLU-backward epilogue: only the dgrad layout (dy W) is instantiated, no split-K
-        if (a_t || !b_t || p.ksplit > 1) return YAT_EINVAL;
-        return nt_variant == 5 ? launch256<false, true, 5, 1>(p, stream) : launch256<false, true, 4, 1>(p, stream);
-    }
-    if (p.dact_z) {                // activation-backward epilogue: dgrad layout only, no split-K
-        if (a_t || !b_t || p.ksplit > 1) return YAT_EINVAL;
-        return nt_variant == 5 ? launch256<false, true, 5, 3>(p, stream) : launch256<false, true, 4, 3>(p, stream);
-    }
-    if (p.rowsum) {                // weight gradient + bias gradient: (1,1) layout, 256 x 256 tile, whole K per workgroup
-        if (!a_t || !b_t || p.ksplit > 1 || nt_variant != 4) return YAT_EINVAL;
-        return launch256<true, true, 4, 4>(p, stream);
-    }
-    if (p.A2) {                    // second operand pair: forward layout, no split-K
-        if (a_t || b_t || p.ksplit > 1) return YAT_EINVAL;
-        return nt_variant == 5 ? launch256<false, false, 5, 5>(p, stream) : launch256<false, false, 4, 5>(p, stream);
-    }
-    if (p.pre_add) {               // adapter addend: only the forward layout (x W^T) is instantiated, no split-K
-        if (a_t || b_t || p.ksplit > 1) return YAT_EINVAL;
-        return nt_variant == 5 ? launch256<false, false, 5, 2>(p, stream) : launch256<false, false, 4, 2>(p, stream);
-    }
-#define YAT_CASE(AT, BT)                                                     \
-    if (a_t == AT && b_t == BT)                                              \
-        return nt_variant == 5 ? launch256<AT, BT, 5>(p, stream) : launch256<AT, BT, 4>(p, stream);
-    YAT_CASE(false, false)
-    YAT_CASE(false, true)
-    YAT_CASE(true, true)
-    YAT_CASE(true, false)
+// Plain dispatch on (layout, tile, class); which combinations exist is GEMM_RULES (gemm_policy.hpp), which gemm_plan has applied.
+int yat_gemm256_launch(int a_t, int b_t, int tile, GemmEpi epi, const GemmP& p, hipStream_t stream) {
+#define YAT_CASE(AT, BT, EPI)                            \
+    if ((a_t != 0) == AT && (b_t != 0) == BT && epi == EPI)  \
+        return tile == 5 ? launch256<AT, BT, 5, EPI>(p, stream) : launch256<AT, BT, 4, EPI>(p, stream);
+    YAT_CASE(false, false, EPI_PLAIN)
+    YAT_CASE(false, true, EPI_PLAIN)
+    YAT_CASE(true, true, EPI_PLAIN)
+    YAT_CASE(true, false, EPI_PLAIN)
+    YAT_CASE(false, true, EPI_GLU_BWD)
+    YAT_CASE(false, false, EPI_PRE_ADD)
+    YAT_CASE(false, true, EPI_ACT_BWD)
+    YAT_CASE(false, false, EPI_PAIR2)
 #undef YAT_CASE
+    if (a_t && b_t && epi == EPI_ROWSUM && tile == 4) return launch256<true, true, 4, EPI_ROWSUM>(p, stream);
     return YAT_EINVAL;
 }

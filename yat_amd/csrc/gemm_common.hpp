@@ -1,6 +1,7 @@
 // Shared by gemm.hip (128x128 tile) and gemm256.hip (256-row tile): launch parameters and the fused epilogue.
 #pragma once
 #include "common.hpp"
+#include "gemm_policy.hpp"
 
 struct GemmP {
     const bf16_t* A; const bf16_t* B; bf16_t* C;
@@ -177,6 +178,6 @@ __device__ __forceinline__ void gemm_epilogue_store8(const GemmP& p, float (&v)[
 }
 
 // gemm256.hip
-int yat_gemm256_launch(int a_t, int b_t, int nt_variant, const GemmP& p, hipStream_t stream);
+int yat_gemm256_launch(int a_t, int b_t, int tile, GemmEpi epi, const GemmP& p, hipStream_t stream);
 // sums the ksplit fp32 slabs and applies the fused epilogue
 int yat_gemm_splitk_reduce(const GemmP& p, hipStream_t stream);

@@ -243,7 +243,7 @@ def linear_wgrad(dy2d, x2d, out, accumulate=False, bias_grad=None, colsum_ws=Non
     (``wgrad_fuses_bias``), from the separate yat_colsum_bf16 pass (``colsum_ws``: its workspace)."""
     M, N = dy2d.shape
     K = x2d.shape[1]
-    # fused only where the shape policy would not split K anyway (>= 96 tiles of 256 x 256: csrc/gemm.hip est_time_256) -- the
+    # fused only where the shape policy would not split K anyway (>= 96 tiles of 256 x 256: csrc/gemm_policy.hpp est_time_256) -- the
     # fused form is one workgroup per tile over the whole K, and a 25-tile, K = 32768 weight gradient (PixArt's D x D) left
     # unsplit makes the weight-gradient stream the critical path (PixArt 228 -> 244 ms when it was fused unconditionally)
     fused = bias_grad is not None and wgrad_fuses_bias(N, K)
