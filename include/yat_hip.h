@@ -411,6 +411,22 @@ int yat_hadamard_scale(int rows, int cols, const void* a, int lda, const void* b
 int yat_hadamard_bwd(int rows, int cols, const void* dd, int ldd, const void* a1, int ld1, const void* a2, int ld2, float scale,
                      void* t1, int ldt1, void* t2, int ldt2, yat_stream_t stream);
 
+/* FourierFT adapters (lora_algo: fourierft, FourierFTConfig at common/trainer.py:231-235) [RECALL peft/tuners/fourierft/layer.py,
+ * parity unpinned]: delta_w[j, k] = s * sum_l c_l cos(2 pi (u_l j / out + v_l k / in)) for n coefficients at fixed positions of an
+ * [out, in] spectrum.  rows = the short dimension, cols = the long one (a caller with out > in passes the transposed problem);
+ * the short dimension is an ordinary yat_gemm_bf16 call against a [rows, 2 rows] cos | -sin matrix, the long one is sparse:
+ *   yat_fourier_expand:   Y[u, k] = bf16(sum_e s c_e cos phi), Y[rows + u, k] = bf16(sum_e s c_e sin phi) over the entries e of
+ *       spectrum row u in CSR order (fp32 sums), phi = 2 pi ((v_e k) mod cols) / cols; rows without an entry are written as zeros;
+ *   yat_fourier_contract: dc[perm[e]] = bf16(s * sum_k (Z[u_e, k] cos phi + Z[rows + u_e, k] sin phi)) -- the adjoint, from
+ *       Z = B^T d_delta_w; coefficients without an entry (the padding of the spectrum vector) are not written.
+ * row_ptr [rows + 1] / col [n] (= v) / perm [n] (= the coefficient's index in `spectrum` / `dc`, below n): int32 on the device;
+ * spectrum / dc bf16 [>= n]; table: fp32 pairs (cos, sin)(2 pi m / cols), m < cols, built by the host in doubles; Y / Z bf16
+ * [2 rows, ld].  cols % 8 == 0, cols and rows <= 46340 (32-bit phases), n >= 1, ld >= cols and ld % 8 == 0. */
+int yat_fourier_expand(int rows, int cols, int n, const int* row_ptr, const int* col, const int* perm, const void* spectrum,
+                       float s, const void* table, void* Y, int ldy, yat_stream_t stream);
+int yat_fourier_contract(int rows, int cols, int n, const int* row_ptr, const int* col, const int* perm, const void* Z, int ldz,
+                         float s, const void* table, void* dc, yat_stream_t stream);
+
 /* DoRA (LoraConfig(..., use_dora=params.lora_use_dora), common/trainer.py:215-220) [RECALL peft/tuners/lora/dora.py]:
  * with lw = lora_B lora_A (an ordinary yat_gemm_bf16 call), u = bf16(W + bf16(scaling*lw)), n_j = bf16(||u_j||) (detached) and
  * s_j = bf16(mag_j / n_j), peft's result = base(x) + (s-1)(x W^T) + s*scaling*lora(x) equals base(x) + x delta^T with

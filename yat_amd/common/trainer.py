@@ -14,8 +14,8 @@ What is different (MI355X-first, documented in DESIGN.md):
   one fused launch pair, so ``clip_grad_norm_`` is a no-op hook here;
 * logging (``tb_writer.SummaryWriter``, TensorBoard event files) keeps the loss on the device and writes the
   scalars YAT_LOG_FLUSH steps at a time, so there is no per-step ``.item()`` stall (:364).
-PEFT adapters (:212-241) are built -- LoRA, DoRA, LoKr, LoHa through ``wrap_adapters`` (yat_amd/lora.py, dora.py, lokr.py,
-loha.py); FourierFT is refused.  Dual-GPU mode, Dreambooth, REPA and DeepSpeed are out of scope.
+PEFT adapters (:212-241) are built -- LoRA, DoRA, LoKr, LoHa, FourierFT through ``wrap_adapters`` (yat_amd/lora.py, dora.py,
+lokr.py, loha.py, fourierft.py).  Dual-GPU mode, Dreambooth, REPA and DeepSpeed are out of scope.
 """
 from __future__ import annotations
 
@@ -183,6 +183,9 @@ def adapter_arithmetic(adapters):
     """One line for logs and bench lines: which rounding order the adapter set in force computes in."""
     if adapters is None:
         return "none"
+    if getattr(adapters, "kind", "") == "FourierFT":
+        return ("fourierft (sparse-spectrum inverse DFT in fp32 from the bf16 spectrum, delta_w rounded to bf16 once, then peft "
+                "order: base output, adapter output and their sum each rounded to bf16; the reference's bf16 ifft2 does not run)")
     if getattr(adapters, "pair", False):
         return "fused_pair (adapter term inside the base GEMM, fp32 sum rounded once; not peft's rounding order)"
     return "pre_add (peft order: base output, adapter output and their sum each rounded to bf16)"
@@ -411,17 +414,19 @@ class Model:
                 from safetensors.torch import load_file
                 with open(os.path.join(p.lora_pretrained, "adapter_config.json")) as f:
                     conf = json.load(f)
-                algo = {"LORA": "lora", "LOKR": "lokr", "LOHA": "loha"}.get(conf.get("peft_type"))
+                algo = {"LORA": "lora", "LOKR": "lokr", "LOHA": "loha", "FOURIERFT": "fourierft"}.get(conf.get("peft_type"))
                 if algo is None:
                     raise NotImplementedError(f"lora_pretrained: peft_type {conf.get('peft_type')!r} is not built")
-                targets, rank = conf["target_modules"], int(conf["r"])
-                alpha = conf["lora_alpha"] if algo == "lora" else conf["alpha"]
-                drop = conf.get("lora_dropout" if algo == "lora" else "module_dropout", 0.0) or 0.0
-                rslora = bool(conf.get("use_rslora", False))
-                dora_saved = bool(conf.get("use_dora", False))
+                if algo != "fourierft":                               # (FourierFT has no rank: its config is read below)
+                    targets, rank = conf["target_modules"], int(conf["r"])
+                    alpha = conf["lora_alpha"] if algo == "lora" else conf["alpha"]
+                    drop = conf.get("lora_dropout" if algo == "lora" else "module_dropout", 0.0) or 0.0
+                    rslora = bool(conf.get("use_rslora", False))
+                    dora_saved = bool(conf.get("use_dora", False))
                 saved = load_file(os.path.join(p.lora_pretrained, "adapter_model.safetensors"))
-            if algo not in ("lokr", "lora", "loha"):
-                raise NotImplementedError(f"lora_algo: {algo} is not built (lokr -- BASELINE config 5 --, lora (+ DoRA) and loha are)")
+            if algo not in ("lokr", "lora", "loha", "fourierft"):
+                raise NotImplementedError(f"lora_algo: {algo} is not built (lokr -- BASELINE config 5 --, lora (+ DoRA), loha and "
+                                          f"fourierft are)")
             pair = adapter_pair(p)
             if algo == "lora" and (getattr(p, "lora_use_dora", False) or dora_saved):      # :214-219 with use_dora=True
                 from ..dora import DoRAAdapters
@@ -433,6 +438,13 @@ class Model:
             elif algo == "loha":                                      # :220-224
                 from ..loha import LoHaAdapters
                 self.adapters = LoHaAdapters(self.model, targets, rank, alpha, module_dropout=drop)
+            elif algo == "fourierft":                                 # :231-237 (lora_rank / lora_alpha / lora_dropout unused)
+                from ..fourierft import FourierFTAdapters
+                if saved is not None:
+                    self.adapters = FourierFTAdapters.from_peft_config(self.model, conf)
+                else:
+                    self.adapters = FourierFTAdapters(self.model, targets, alpha=getattr(p, "fourierft_alpha", 0.01), scaling=1.0,
+                                                      norm="ortho")
             else:                                                     # :226-230
                 from ..lokr import LoKrAdapters
                 self.adapters = LoKrAdapters(self.model, targets, rank, alpha, module_dropout=drop, pair=pair)

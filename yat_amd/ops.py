@@ -325,6 +325,37 @@ def hadamard_bwd(dd2d, a1, a2, scale, t1, t2):
     _l.check(rc, "yat_hadamard_bwd")
 
 
+def _chk_i32(*ts):
+    for t in ts:
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("expected a contiguous int32 tensor on the GPU")
+
+
+def fourier_expand(row_ptr, col, perm, spectrum, s, table, y):
+    """y [2 rows, cols] (a view with row stride) <- the sparse half of FourierFT's inverse DFT: the cos | sin sums of every
+    spectrum row over its CSR entries (yat_fourier_expand).  ``spectrum`` holds at least ``perm.numel()`` coefficients."""
+    _chk_bf16(spectrum, y)
+    _chk_i32(row_ptr, col, perm)
+    rows, cols, n = row_ptr.numel() - 1, y.shape[1], perm.numel()
+    assert y.shape[0] == 2 * rows and table.dtype == torch.float32 and table.shape == (cols, 2) and spectrum.numel() >= n
+    rc = _lib().yat_fourier_expand(rows, cols, n, _p(row_ptr), _p(col), _p(perm), _p(spectrum), float(s), _p(table), _p(y),
+                                   y.stride(0), _stream())
+    _l.check(rc, "yat_fourier_expand")
+    return y
+
+
+def fourier_contract(row_ptr, col, perm, z, s, table, dc):
+    """dc[perm[e]] <- s * sum_k (z[u_e, k] cos + z[rows + u_e, k] sin): the adjoint of ``fourier_expand`` (yat_fourier_contract)."""
+    _chk_bf16(z, dc)
+    _chk_i32(row_ptr, col, perm)
+    rows, cols, n = row_ptr.numel() - 1, z.shape[1], perm.numel()
+    assert z.shape[0] == 2 * rows and table.dtype == torch.float32 and table.shape == (cols, 2) and dc.numel() >= n
+    rc = _lib().yat_fourier_contract(rows, cols, n, _p(row_ptr), _p(col), _p(perm), _p(z), z.stride(0), float(s), _p(table),
+                                     _p(dc), _stream())
+    _l.check(rc, "yat_fourier_contract")
+    return dc
+
+
 def dora_delta(w, lw, mag, scaling, delta, s_buf, n_buf):
     """delta_j = s_j (W_j + scaling lw_j) - W_j with s_j = mag_j / ||W_j + scaling lw_j|| (yat_dora_delta); s, n -> fp32 buffers."""
     _chk_bf16(w, lw, mag, delta)
